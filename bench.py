@@ -16,7 +16,13 @@ value = solved instances of all ranks in the timed steps / max-over-ranks wall t
 With --workload stress: BASELINE.json configs[4], the same NLP at N = 256 knots with the 2-256x4-1 ReLU SDF
 MLP (seeded, MlpWeights.stress_sdf_mlp), 8192 instances per GPU; the roofline is then the MLP's (f32 MFMA).
 
-    python bench.py [--gpus N --steps K --warmup W --batch B --workload metric|stress]
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what the headline figure
+does not need: the CPU baseline (the oracle on a sample of the first timed batch, after the timed region), reported
+as `cpu_baseline`.  --dump-outputs DIR writes what the last timed step's solve returned (X, U, S, cost, status, iters
+of its batch; a fixed seeded sample of its instances where they exceed 32 MiB) as DIR/<name>.npy in float64; with
+the same arguments the inputs are the same from run to run, so two builds can be compared output for output.
+
+    python bench.py [--gpus N --steps K --warmup W --batch B --workload metric|stress --full --dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -68,10 +74,19 @@ def parse():
                          "driver's --steps 20 --warmup 5 run fits its 600 s budget; 65536 measures ~7 %% more; stress default "
                          "8192 = 65536 over 8 GPUs)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (cpu_baseline; the "
+                         "--cpu-* options configure it).  Off by default: a plain run sets up, warms up, times the steps "
+                         "and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step's solve returned (X, U, S, cost, status, "
+                         "iters of rank 0's last batch; a fixed seeded sample of its instances where they exceed 32 MiB, "
+                         "listed in sample_index.npy) as DIR/<name>.npy in float64")
     ap.add_argument("--cpu-sample", type=int, default=None,
-                    help="instances for the CPU baseline on all threads (0 = skip; default 32; 16 stress)")
+                    help="--full: instances for the CPU baseline on all threads (0 = skip; default 32; 16 stress)")
     ap.add_argument("--cpu-sample-1core", type=int, default=None,
-                    help="at least this many instances for the single-core CPU baseline, one at a time until ~8 s (default 2; 1 stress)")
+                    help="--full: at least this many instances for the single-core CPU baseline, one at a time until ~8 s "
+                         "(default 2; 1 stress)")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="CPU-baseline threads (default: the host's CPU share: min(affinity, cgroup cpu.max quota))")
     ap.add_argument("--cpu-overlap", choices=["on", "off"], default="off",
@@ -127,6 +142,27 @@ def timed_loop(step, steps, warmup, world, sync, device, after_warmup=None):
     if world > 1:
         dist.barrier()
     return out, max_over_ranks(time.perf_counter() - t0, device)
+
+
+DUMP_KEYS = ("X", "U", "S", "cost", "status", "iters")  # what solve_batch returns
+DUMP_MAX_BYTES = 32 << 20
+
+
+def dump_outputs(path, r, batch, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the last `batch` instances of the solve result `r` (the last timed step's batch; under
+    continuous batching the call's result holds all the timed batches in order) as path/<name>.npy, float64.  Where
+    they exceed max_bytes, a sample of the instances drawn once with numpy's PCG64 at seed 0 (the same instances
+    whatever the run's --seed), in ascending order; sample_index.npy lists their indices within the batch."""
+    total = int(r["status"].shape[0])
+    per_row = 8 * sum(int(np.prod(r[k].shape[1:])) for k in DUMP_KEYS)
+    n = max(1, min(batch, max_bytes // per_row))
+    idx = np.arange(batch) if n == batch else np.sort(np.random.default_rng(0).choice(batch, n, replace=False))
+    sel = torch.as_tensor(total - batch + idx, dtype=torch.long, device=r["status"].device)
+    os.makedirs(path, exist_ok=True)
+    for k in DUMP_KEYS:
+        np.save(os.path.join(path, k + ".npy"), r[k].index_select(0, sel).double().cpu().numpy())
+    np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    return n
 
 
 def ric_bytes_per_solve(prob, nr=2):
@@ -332,7 +368,7 @@ def main():
     # the CPU baseline (rank 0 of a one-rank run, not the stress estimate, which needs the GPU run's iteration counts)
     # overlaps the warm-up: a host thread runs the oracle (ctypes releases the GIL) while the GPU warms up
     cpu_box, cpu_thread = {}, None
-    cpu_here = rank == 0 and world == 1 and a.cpu_sample > 0
+    cpu_here = a.full and rank == 0 and world == 1 and a.cpu_sample > 0
     if cpu_here and not stress and a.cpu_overlap == "on" and warm_calls > 0:
         import threading
 
@@ -361,6 +397,10 @@ def main():
 
     results, elapsed = timed_loop(timed_call, len(calls), warm_calls, world, sync, dev, after_warmup=join_cpu)
     set_timing(False)
+    if a.dump_outputs and rank == 0:
+        n_dump = dump_outputs(a.dump_outputs, results[-1], a.batch)
+        print(f"[bench] wrote {n_dump} of the last step's {a.batch} instances to {a.dump_outputs}", file=sys.stderr,
+              flush=True)
     st_all = torch.cat([x["status"] for x in results]).long()
     it_all = torch.cat([x["iters"] for x in results]).double()
     solved_total = sum_over_ranks(int((st_all == 0).sum().item()), dev)
@@ -570,6 +610,7 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": elapsed / a.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",

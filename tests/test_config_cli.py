@@ -9,7 +9,9 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CFG = os.path.join(HERE, "golden", "configs")
-REF = "/root/reference/src/nlotrajectories/benchmarks"
+# the reference's own scenario files (settings only), stored with the suite: benchmarks/ = its six benchmark YAMLs,
+# configs/ = its three malformed ones
+REF = os.path.join(HERE, "golden", "reference_yaml")
 
 
 def test_restated_configs_map_to_benchmarks():
@@ -27,17 +29,18 @@ def test_restated_configs_map_to_benchmarks():
         assert bytes(p.to_c()) == bytes(q.to_c())
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 def test_reference_yaml_files_validate():
     from nlotrajectories_amd.config import Config
 
-    files = sorted(glob.glob(os.path.join(REF, "*.yaml")))
+    files = sorted(glob.glob(os.path.join(REF, "benchmarks", "*.yaml")))
     assert len(files) == 6
     for f in files:
         c = Config.load(f)
         assert c.solver.type == "ipopt" and c.solver.initializer.choice.mode == "rrt"
         c.to_problem()
-    for f in sorted(glob.glob("/root/reference/configs/*.yaml")):
+    bad = sorted(glob.glob(os.path.join(REF, "configs", "*.yaml")))
+    assert len(bad) == 3
+    for f in bad:
         with pytest.raises(Exception):
             Config.load(f)
 
