@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 15
+#define NLOT_ABI_VERSION 16
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -327,6 +327,49 @@ size_t nlot_rrt_workspace_size(const NlotRrtOptions* opt, int64_t B);
  * mode). Asynchronous on `stream`. */
 int32_t nlot_rrt_init(const NlotProblem* prob, const NlotRrtOptions* opt, const double* x0, const double* xg,
                       double* X_init, int32_t* ok, int64_t B, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- batched trajectory verification against the exact scene (ABI v16) ------------------------
+ * NLOT_SOLVED says the interior-point method converged on the NLP; these say what the trajectory does in the scene:
+ * the obstacle constraint is soft with use_slack (runner.py:66-77), it holds at the N + 1 knots and the footprint's
+ * corners only (densify_polygon is called with num_points = 0, geometry.py:110-112), and in learned-SDF mode it is a
+ * constraint on the net.  The check samples: it bounds, it does not prove. */
+typedef struct NlotVerifyOptions {
+    int32_t sub;           /* poses per interval, >= 1 (default 8) */
+    int32_t edge_points;   /* interior points per footprint edge, >= 0 (default 3) */
+    double clearance_min;  /* NLOT_VERIFY_COLLISION if clearance < this (0) */
+    double defect_tol;     /* NLOT_VERIFY_DEFECT if defect > this (1e-4 = constr_viol_tol) */
+    double bound_tol;      /* NLOT_VERIFY_UBOUND / _BOUNDARY if ubound / boundary > this (1e-4) */
+} NlotVerifyOptions;
+#define NLOT_VERIFY_COLLISION 1  /* clearance < clearance_min */
+#define NLOT_VERIFY_CONTAINS 2   /* an obstacle's centre (circle, square) or vertex (polygon, trapezoid) lies strictly
+                                    inside the footprint at a sampled pose (polygon bodies); clearance is unchanged */
+#define NLOT_VERIFY_DEFECT 4
+#define NLOT_VERIFY_UBOUND 8
+#define NLOT_VERIFY_BOUNDARY 16
+#define NLOT_VERIFY_NONFINITE 32 /* a non-finite entry in the instance's X, U (or x0, xg): the four double outputs are
+                                    NaN, where is -1 and no other flag is set */
+/* Fill `opt` with the defaults documented above. */
+void nlot_default_verify_options(NlotVerifyOptions* opt);
+
+/* Verify B trajectories of `prob` against the scene's EXACT SDF (MultiObstacle.sdf, casadi.py:381-383, margins
+ * subtracted) in prob->obs, whatever prob->sdf_kind says (like nlot_rrt_init).  Per instance:
+ *   clearance  min of the exact SDF over P = N sub + 1 poses x the footprint points.  Pose s < N sub is
+ *              x_k + tau (x_{k+1} - x_k), k = s / sub, tau = (s mod sub) / sub; pose N sub is knot N; components 0, 1
+ *              and, for a polygon body, the heading 2 (interpolated linearly, no angle wrapping).  Footprint: the one
+ *              point of NLOT_SHAPE_DOT, or per edge corner i and edge_points interior points at t = j / (edge_points + 1)
+ *              towards corner i + 1 (densify_polygon, geometry.py:85-105, with num_points = edge_points)
+ *   where      pose index of that minimum (the lowest on exact ties); where / sub is the knot at or before it
+ *   defect     max over k and components of |x_{k+1} - Phi(x_k, u_k)|, Phi the problem's defect map (prob->integrator)
+ *   ubound     max over k, i of max(umin_i - u, u - umax_i, 0)
+ *   boundary   max |X_0 - x0| and |X_N - xg| (component 2 of the latter only with enforce_heading, runner.py:50-56);
+ *              0 when x0 and xg are NULL
+ *   flags      NLOT_VERIFY_* bits; 0 = the trajectory passed every check
+ *   X [B][N+1][nx], U [B][N][nu], x0, xg [B][nx] (both or neither) fp64 device; the six outputs [B] device, all required.
+ * Asynchronous on `stream`; no workspace, no global state (a stream-ordered temporary holds the problem).
+ * NLOT_ERR_INVALID before any device call for: n_obs == 0, null pointers, sub < 1, edge_points < 0, exactly one of
+ * x0 / xg, B outside 1 .. 2^26, a per-instance sample count beyond int32. */
+int32_t nlot_verify_batch(const NlotProblem* prob, const NlotVerifyOptions* opt, const double* X, const double* U,
+                          const double* x0, const double* xg, double* clearance, int32_t* where, double* defect,
+                          double* ubound, double* boundary, int32_t* flags, int64_t B, void* stream);
 casadi_int_t nn_sdf_n_in(void);
 casadi_int_t nn_sdf_n_out(void);
 const casadi_int_t* nn_sdf_sparsity_in(casadi_int_t i);

@@ -118,3 +118,20 @@ class NlotRrtOptions(C.Structure):
     """include/nlot.h NlotRrtOptions (RRTInitializer arguments, trajectory_initialization.py:68-81)."""
     _fields_ = [("bounds", (C.c_double * 2) * 2), ("step_size", C.c_double), ("margin", C.c_double),
                 ("goal_sample_rate", C.c_double), ("seed", C.c_uint64), ("max_iter", C.c_int32), ("first_instance", C.c_int32)]
+
+
+# nlot_verify_batch (include/nlot.h, ABI v16): flag bits of the per-instance verdict
+VERIFY_COLLISION, VERIFY_CONTAINS, VERIFY_DEFECT, VERIFY_UBOUND, VERIFY_BOUNDARY, VERIFY_NONFINITE = 1, 2, 4, 8, 16, 32
+VERIFY_FLAG_NAMES = {1: "collision", 2: "contains", 4: "defect", 8: "ubound", 16: "boundary", 32: "nonfinite"}
+
+
+class NlotVerifyOptions(C.Structure):
+    """include/nlot.h NlotVerifyOptions."""
+    _fields_ = [("sub", C.c_int32), ("edge_points", C.c_int32), ("clearance_min", C.c_double),
+                ("defect_tol", C.c_double), ("bound_tol", C.c_double)]
+
+
+def verify_options(sub=8, edge_points=3, clearance_min=0.0, defect_tol=1e-4, bound_tol=1e-4) -> NlotVerifyOptions:
+    """The defaults of nlot_default_verify_options (defect_tol = the solver's constr_viol_tol)."""
+    return NlotVerifyOptions(sub=int(sub), edge_points=int(edge_points), clearance_min=float(clearance_min),
+                             defect_tol=float(defect_tol), bound_tol=float(bound_tol))

@@ -24,6 +24,7 @@ EXPORTED = [
     "nn_sdf_sparsity_out", "nn_sdf", "jac_nn_sdf_n_in", "jac_nn_sdf_n_out", "jac_nn_sdf",
     "adj1_nn_sdf_n_in", "adj1_nn_sdf_n_out", "adj1_nn_sdf", "jac_adj1_nn_sdf_n_in",
     "jac_adj1_nn_sdf_n_out", "jac_adj1_nn_sdf", "nlot_rrt_workspace_size", "nlot_rrt_init",
+    "nlot_default_verify_options", "nlot_verify_batch",
 ]
 
 
@@ -77,9 +78,14 @@ def lib():
     L.nlot_rrt_init.argtypes = [C.POINTER(_abi.NlotProblem), C.POINTER(_abi.NlotRrtOptions), vp, vp, vp, vp, C.c_int64,
                                 vp, C.c_size_t, vp]
     L.nlot_rrt_init.restype = C.c_int32
+    L.nlot_default_verify_options.argtypes = [C.POINTER(_abi.NlotVerifyOptions)]
+    L.nlot_default_verify_options.restype = None
+    L.nlot_verify_batch.argtypes = [C.POINTER(_abi.NlotProblem), C.POINTER(_abi.NlotVerifyOptions), vp, vp, vp, vp, vp,
+                                    vp, vp, vp, vp, vp, C.c_int64, vp]
+    L.nlot_verify_batch.restype = C.c_int32
     L.nlot_casadi_bind.argtypes = [vp]
     L.nlot_casadi_bind.restype = C.c_int32
-    if L.nlot_abi_version() != 15:
+    if L.nlot_abi_version() != 16:
         raise NlotError("libnlot.so ABI version mismatch")
     _lib = L
     return L

@@ -13,7 +13,9 @@ Differences from the reference, all loud:
     by MlpWeights.save, e.g. data/b6_mlp128_seed0.npz, or the shipped artefact with --weights artefact);
   * solver.type sqpmethod is not provided (the reference's default benchmarks all use ipopt);
   * plots are not produced; the CSV row always carries all 20 header columns (the reference writes 17
-    values under a 20-column header).
+    values under a 20-column header);
+  * --verify (off by default) measures the returned trajectory against the scene's exact SDF between the knots
+    and along the footprint's edges (verify.py) and prints three more lines; nothing else changes.
 """
 from __future__ import annotations
 
@@ -58,9 +60,21 @@ def _fmt(v, spec):
     return "None" if v is None else format(v, spec)
 
 
+def _print_verification(prob, r, x0, xg, sub, edge_points):
+    """--verify: the returned trajectory against the scene's exact SDF (verify.py), for a failed solve too."""
+    from .verify import verify_batch
+
+    v = verify_batch(prob, r["X"], r["U"], x0=x0, xg=xg, sub=sub, edge_points=edge_points)
+    flags = int(v["flags"][0])
+    print(f"Exact clearance: {float(v['clearance'][0])} at knot {int(v['where'][0]) // sub}")
+    print("Max dynamics defect:", float(v["defect"][0]))
+    print("Collision-free:", not flags & (_abi.VERIFY_COLLISION | _abi.VERIFY_CONTAINS | _abi.VERIFY_NONFINITE))
+
+
 def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="results", verbose=True,
-                  options=None, metrics=True):
-    """Returns (X_opt [nx, N+1], U_opt [nu, N], status str) like RunBenchmark.run (runner.py:148-153)."""
+                  options=None, metrics=True, verify=False, verify_sub=8, verify_edge_points=3):
+    """Returns (X_opt [nx, N+1], U_opt [nu, N], status str) like RunBenchmark.run (runner.py:148-153).
+    verify=True also prints the trajectory's exact clearance, dynamics defect and collision verdict."""
     config_path = Path(config_path)
     cfg = Config.load(config_path)
     if cfg.solver.type != "ipopt":
@@ -108,6 +122,8 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
             names = {1: "maximum iterations", 2: "line search failure", 3: "numerical failure"}
             print(f"[IPOPT Error] {names.get(st, st)} after {int(r['iters'][0])} iterations")
             print("Dynamics violation:", np.linalg.norm(X[:, 1:] - X[:, :-1] - prob.dt * _f(prob, X[:, :-1], U)))
+            if verify:
+                _print_verification(prob, r, x0, xg, verify_sub, verify_edge_points)
         return X, U, status
     obj = float(r["cost"][0])
     if not verbose:
@@ -119,6 +135,8 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
         print(f"{name}:", v)
     print("Optimization complete.")
     print("Final state:", X[:, -1])
+    if verify:
+        _print_verification(prob, r, x0, xg, verify_sub, verify_edge_points)
     out = Path(results_dir)
     out.mkdir(parents=True, exist_ok=True)
     f = out / f"{config_path.stem}_results.csv"
@@ -164,8 +182,14 @@ def main(argv=None):
                     help="override the YAML initializer (yaml = the config's own, rrt for every shipped one)")
     ap.add_argument("--weights", type=str, default=None, help="learned-SDF weights: 'train' (NNObstacleTrainer), an .npz, or 'artefact'")
     ap.add_argument("--results", type=str, default="results")
+    ap.add_argument("--verify", action="store_true",
+                    help="check the returned trajectory against the scene's exact SDF between the knots and along the "
+                         "footprint's edges, and its dynamics defect (verify.py)")
+    ap.add_argument("--verify-sub", type=int, default=8, help="--verify: poses sampled per interval")
+    ap.add_argument("--verify-edge-points", type=int, default=3, help="--verify: interior points per footprint edge")
     a = ap.parse_args(argv)
-    run_benchmark(Path(a.config), initializer=a.initializer, weights=a.weights, results_dir=a.results)
+    run_benchmark(Path(a.config), initializer=a.initializer, weights=a.weights, results_dir=a.results, verify=a.verify,
+                  verify_sub=a.verify_sub, verify_edge_points=a.verify_edge_points)
 
 
 if __name__ == "__main__":

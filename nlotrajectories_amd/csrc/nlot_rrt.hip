@@ -15,6 +15,7 @@
 // (seed, instance, iteration, draw) — the same stream oracle/rrt_oracle.py draws, so the trees are comparable.
 #include <cmath>
 
+#include "nlot_device.h"
 #include "nlot_internal.h"
 
 namespace nlot {
@@ -31,43 +32,7 @@ __device__ inline double u01(uint64_t key, int it, int k) {
     return (double)(mix64(key ^ (uint64_t)(4 * (int64_t)it + k)) >> 11) * 0x1.0p-53;
 }
 
-// MultiObstacle.sdf (casadi.py:381-383): the minimum of the obstacles' exact SDFs (a group's too)
-//   circle  casadi.py:33-38      square  casadi.py:54-67
-//   polygon / trapezoid  PolygonObstacle.sdf casadi.py:135-148: distance to the boundary, negative inside
-__device__ double exact_sdf(const NlotProblem& p, double x, double y) {
-    double best = INFINITY;
-    for (int i = 0; i < p.n_obs; ++i) {
-        const NlotObstacle& o = p.obs[i];
-        double v;
-        if (o.type == NLOT_OBS_CIRCLE) {
-            const double dx = x - o.cx, dy = y - o.cy;
-            v = sqrt(dx * dx + dy * dy) - (o.size + o.margin);
-        } else if (o.type == NLOT_OBS_SQUARE) {
-            const double half = o.size / 2 + o.margin;
-            const double dx = fabs(x - o.cx) - half, dy = fabs(y - o.cy) - half;
-            const double ox = fmax(dx, 0.0), oy = fmax(dy, 0.0);
-            v = sqrt(ox * ox + oy * oy) + fmin(fmax(dx, dy), 0.0);
-        } else {
-            const double(*V)[2] = p.verts + o.v0;
-            double d = INFINITY;
-            bool inside = false;
-            for (int e = 0; e < o.nv; ++e) {
-                const int e1 = e + 1 < o.nv ? e + 1 : 0;
-                const double x0 = V[e][0], y0 = V[e][1], x1 = V[e1][0], y1 = V[e1][1];
-                const double ex = x1 - x0, ey = y1 - y0;
-                double t = ((x - x0) * ex + (y - y0) * ey) / (ex * ex + ey * ey);
-                t = fmin(fmax(t, 0.0), 1.0);
-                const double qx = x - (x0 + t * ex), qy = y - (y0 + t * ey);
-                d = fmin(d, sqrt(qx * qx + qy * qy));
-                if ((y0 > y) != (y1 > y) && x < x0 + (y - y0) * ex / (y1 - y0)) inside = !inside;
-            }
-            v = (inside ? -d : d) - o.margin;
-        }
-        best = fmin(best, v);
-    }
-    return best;
-}
-
+// exact_sdf (MultiObstacle.sdf, casadi.py:381-383): nlot_device.h, shared with the verification kernel
 __device__ inline int wave_any(int v) {
     for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
     return v;
