@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 16
+#define NLOT_ABI_VERSION 17
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -370,6 +370,62 @@ void nlot_default_verify_options(NlotVerifyOptions* opt);
 int32_t nlot_verify_batch(const NlotProblem* prob, const NlotVerifyOptions* opt, const double* X, const double* U,
                           const double* x0, const double* xg, double* clearance, int32_t* where, double* defect,
                           double* ubound, double* boundary, int32_t* flags, int64_t B, void* stream);
+
+/* ---- batched forward rollout of the returned controls through the dynamics (ABI v17) ------------
+ * What a user executes is U.  nlot_verify_batch measures the plan X (its `defect` is X against the problem's own
+ * discrete map, so a perfect Euler plan passes); the continuous-time robot fed U under zero-order hold does not
+ * follow an Euler plan: it drifts from it at first order in dt.  The rollout integrates the problem's continuous
+ * dynamics from X_0 under U and measures the rolled motion.  It is RK4 at h = dt / substeps,
+ * not the exact flow; it is zero-order hold and open loop (no feedback); and it samples poses and footprint points,
+ * so section 10's half-spacing bound applies to its clearance too: it bounds, it does not prove. */
+typedef struct NlotRolloutOptions {
+    int32_t substeps;      /* classical RK4 steps per interval, >= 1 (default 8) */
+    int32_t edge_points;   /* interior points per footprint edge, >= 0 (default 3) */
+    double clearance_min;  /* NLOT_ROLLOUT_COLLISION if clearance < this (0) */
+    double deviation_tol;  /* NLOT_ROLLOUT_DEVIATION if deviation > this (+inf: off) */
+    double goal_tol;       /* NLOT_ROLLOUT_GOAL if goal_error > this (+inf: off) */
+} NlotRolloutOptions;
+#define NLOT_ROLLOUT_COLLISION 1
+#define NLOT_ROLLOUT_CONTAINS 2
+#define NLOT_ROLLOUT_DEVIATION 4
+#define NLOT_ROLLOUT_GOAL 8
+#define NLOT_ROLLOUT_NONFINITE 32  /* non-finite input (X, U, xg) */
+#define NLOT_ROLLOUT_DIVERGED 64   /* finite input, but a rolled state became non-finite */
+/* Fill `opt` with the defaults documented above. */
+void nlot_default_rollout_options(NlotRolloutOptions* opt);
+
+/* Roll the controls of B trajectories of `prob` forward through its continuous dynamics f.  Per instance:
+ *   rolled motion  starts at X[b][0]; pose s, s = 0 .. N substeps, is the state after s classical RK4 steps
+ *              x + h (k1 + 2 k2 + 2 k3 + k4) / 6 of size h = dt / substeps, with the control U[b][s / substeps] held
+ *              constant over its interval.  This is the flow WHATEVER prob->integrator says; at substeps = 1 the
+ *              rolled knots of an NLOT_INTEG_RK4 problem are exactly that problem's defect map.  Rolled knot k is
+ *              pose k substeps
+ *   X_roll     [B][N+1][nx] the rolled knots, or NULL
+ *   clearance  min of the scene's exact SDF (as in nlot_verify_batch) over the P = N substeps + 1 rolled poses x the
+ *              footprint points of nlot_verify_batch (the one point of NLOT_SHAPE_DOT, or per edge corner i and
+ *              edge_points interior points at t = j / (edge_points + 1)); the heading is component 2 of the rolled
+ *              state.  Unlike nlot_verify_batch, n_obs == 0 is allowed: clearance = +inf, where = -1 and neither
+ *              COLLISION nor CONTAINS is set (a learned-SDF problem without a scene can still be rolled for its
+ *              deviation and goal error)
+ *   where      pose index of that minimum (the lowest on exact ties); where / substeps is the knot at or before it
+ *   NLOT_ROLLOUT_CONTAINS  the test of NLOT_VERIFY_CONTAINS at the rolled poses
+ *   deviation  max over k = 0 .. N of hypot(X_roll_k[0] - X_k[0], X_roll_k[1] - X_k[1])
+ *   dev_where  the lowest k attaining it (0 with deviation 0 when nothing departs)
+ *   goal_error hypot of the position difference between rolled knot N and g; g = xg[b] if xg is given, else X[b][N]
+ *   flags      NLOT_ROLLOUT_* bits; 0 = passed.  A non-finite entry in the instance's X, U (or xg) gives
+ *              NLOT_ROLLOUT_NONFINITE alone, the four double outputs NaN and where = dev_where = -1.  Finite input
+ *              whose rolled state turns non-finite gives NLOT_ROLLOUT_DIVERGED alone with the same NaN / -1 outputs;
+ *              X_roll is unspecified from that knot on
+ *   X [B][N+1][nx], U [B][N][nu], xg [B][nx] or NULL: fp64 device; the six outputs [B] device, all required.
+ * An instance's outputs depend on that instance's inputs only: they are bitwise the same whatever B is and wherever
+ * in the batch the instance sits.
+ * Asynchronous on `stream`; no workspace, no global state (a stream-ordered temporary holds the problem).
+ * NLOT_ERR_INVALID before any device call for: null prob or opt, substeps < 1, edge_points < 0, an invalid problem
+ * (the checks of nlot_verify_batch without its n_obs == 0 refusal), B outside 1 .. 2^26, a null required pointer
+ * (everything but xg and X_roll), (N substeps + 1) * n_body (1 + edge_points) beyond int32. */
+int32_t nlot_rollout_batch(const NlotProblem* prob, const NlotRolloutOptions* opt, const double* X, const double* U,
+                           const double* xg, double* X_roll, double* clearance, int32_t* where, double* deviation,
+                           int32_t* dev_where, double* goal_error, int32_t* flags, int64_t B, void* stream);
 casadi_int_t nn_sdf_n_in(void);
 casadi_int_t nn_sdf_n_out(void);
 const casadi_int_t* nn_sdf_sparsity_in(casadi_int_t i);

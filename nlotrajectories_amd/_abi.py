@@ -135,3 +135,21 @@ def verify_options(sub=8, edge_points=3, clearance_min=0.0, defect_tol=1e-4, bou
     """The defaults of nlot_default_verify_options (defect_tol = the solver's constr_viol_tol)."""
     return NlotVerifyOptions(sub=int(sub), edge_points=int(edge_points), clearance_min=float(clearance_min),
                              defect_tol=float(defect_tol), bound_tol=float(bound_tol))
+
+
+# nlot_rollout_batch (include/nlot.h, ABI v17): flag bits of the per-instance verdict
+ROLLOUT_COLLISION, ROLLOUT_CONTAINS, ROLLOUT_DEVIATION, ROLLOUT_GOAL, ROLLOUT_NONFINITE, ROLLOUT_DIVERGED = 1, 2, 4, 8, 32, 64
+ROLLOUT_FLAG_NAMES = {1: "collision", 2: "contains", 4: "deviation", 8: "goal", 32: "nonfinite", 64: "diverged"}
+
+
+class NlotRolloutOptions(C.Structure):
+    """include/nlot.h NlotRolloutOptions."""
+    _fields_ = [("substeps", C.c_int32), ("edge_points", C.c_int32), ("clearance_min", C.c_double),
+                ("deviation_tol", C.c_double), ("goal_tol", C.c_double)]
+
+
+def rollout_options(substeps=8, edge_points=3, clearance_min=0.0, deviation_tol=float("inf"),
+                    goal_tol=float("inf")) -> NlotRolloutOptions:
+    """The defaults of nlot_default_rollout_options (the deviation and goal thresholds are off)."""
+    return NlotRolloutOptions(substeps=int(substeps), edge_points=int(edge_points), clearance_min=float(clearance_min),
+                              deviation_tol=float(deviation_tol), goal_tol=float(goal_tol))

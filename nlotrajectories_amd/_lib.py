@@ -24,7 +24,7 @@ EXPORTED = [
     "nn_sdf_sparsity_out", "nn_sdf", "jac_nn_sdf_n_in", "jac_nn_sdf_n_out", "jac_nn_sdf",
     "adj1_nn_sdf_n_in", "adj1_nn_sdf_n_out", "adj1_nn_sdf", "jac_adj1_nn_sdf_n_in",
     "jac_adj1_nn_sdf_n_out", "jac_adj1_nn_sdf", "nlot_rrt_workspace_size", "nlot_rrt_init",
-    "nlot_default_verify_options", "nlot_verify_batch",
+    "nlot_default_verify_options", "nlot_verify_batch", "nlot_default_rollout_options", "nlot_rollout_batch",
 ]
 
 
@@ -83,9 +83,14 @@ def lib():
     L.nlot_verify_batch.argtypes = [C.POINTER(_abi.NlotProblem), C.POINTER(_abi.NlotVerifyOptions), vp, vp, vp, vp, vp,
                                     vp, vp, vp, vp, vp, C.c_int64, vp]
     L.nlot_verify_batch.restype = C.c_int32
+    L.nlot_default_rollout_options.argtypes = [C.POINTER(_abi.NlotRolloutOptions)]
+    L.nlot_default_rollout_options.restype = None
+    L.nlot_rollout_batch.argtypes = [C.POINTER(_abi.NlotProblem), C.POINTER(_abi.NlotRolloutOptions), vp, vp, vp, vp, vp,
+                                     vp, vp, vp, vp, vp, C.c_int64, vp]
+    L.nlot_rollout_batch.restype = C.c_int32
     L.nlot_casadi_bind.argtypes = [vp]
     L.nlot_casadi_bind.restype = C.c_int32
-    if L.nlot_abi_version() != 16:
+    if L.nlot_abi_version() != 17:
         raise NlotError("libnlot.so ABI version mismatch")
     _lib = L
     return L

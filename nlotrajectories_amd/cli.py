@@ -15,7 +15,9 @@ Differences from the reference, all loud:
   * plots are not produced; the CSV row always carries all 20 header columns (the reference writes 17
     values under a 20-column header);
   * --verify (off by default) measures the returned trajectory against the scene's exact SDF between the knots
-    and along the footprint's edges (verify.py) and prints three more lines; nothing else changes.
+    and along the footprint's edges (verify.py) and prints three more lines; nothing else changes;
+  * --rollout (off by default) rolls the returned controls forward through the continuous dynamics (rollout.py:
+    sub-stepped RK4, zero-order hold, open loop) and prints four more lines, after --verify's; nothing else changes.
 """
 from __future__ import annotations
 
@@ -71,10 +73,25 @@ def _print_verification(prob, r, x0, xg, sub, edge_points):
     print("Collision-free:", not flags & (_abi.VERIFY_COLLISION | _abi.VERIFY_CONTAINS | _abi.VERIFY_NONFINITE))
 
 
+def _print_rollout(prob, r, xg, substeps, edge_points):
+    """--rollout: the returned controls rolled through the continuous dynamics (rollout.py), for a failed solve too."""
+    from .rollout import rollout_batch
+
+    v = rollout_batch(prob, r["X"], r["U"], xg=xg, substeps=substeps, edge_points=edge_points)
+    flags = int(v["flags"][0])
+    print(f"Rollout clearance: {float(v['clearance'][0])} at knot {int(v['where'][0]) // substeps}")
+    print(f"Rollout deviation: {float(v['deviation'][0])} at knot {int(v['dev_where'][0])}")
+    print("Rollout goal error:", float(v["goal_error"][0]))
+    print("Rollout collision-free:", not flags & (_abi.ROLLOUT_COLLISION | _abi.ROLLOUT_CONTAINS |
+                                                  _abi.ROLLOUT_NONFINITE | _abi.ROLLOUT_DIVERGED))
+
+
 def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="results", verbose=True,
-                  options=None, metrics=True, verify=False, verify_sub=8, verify_edge_points=3):
+                  options=None, metrics=True, verify=False, verify_sub=8, verify_edge_points=3, rollout=False,
+                  rollout_substeps=8, rollout_edge_points=3):
     """Returns (X_opt [nx, N+1], U_opt [nu, N], status str) like RunBenchmark.run (runner.py:148-153).
-    verify=True also prints the trajectory's exact clearance, dynamics defect and collision verdict."""
+    verify=True also prints the trajectory's exact clearance, dynamics defect and collision verdict; rollout=True the
+    clearance, deviation from the plan and goal error of the controls rolled through the continuous dynamics."""
     config_path = Path(config_path)
     cfg = Config.load(config_path)
     if cfg.solver.type != "ipopt":
@@ -124,6 +141,8 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
             print("Dynamics violation:", np.linalg.norm(X[:, 1:] - X[:, :-1] - prob.dt * _f(prob, X[:, :-1], U)))
             if verify:
                 _print_verification(prob, r, x0, xg, verify_sub, verify_edge_points)
+            if rollout:
+                _print_rollout(prob, r, xg, rollout_substeps, rollout_edge_points)
         return X, U, status
     obj = float(r["cost"][0])
     if not verbose:
@@ -137,6 +156,8 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
     print("Final state:", X[:, -1])
     if verify:
         _print_verification(prob, r, x0, xg, verify_sub, verify_edge_points)
+    if rollout:
+        _print_rollout(prob, r, xg, rollout_substeps, rollout_edge_points)
     out = Path(results_dir)
     out.mkdir(parents=True, exist_ok=True)
     f = out / f"{config_path.stem}_results.csv"
@@ -187,9 +208,15 @@ def main(argv=None):
                          "footprint's edges, and its dynamics defect (verify.py)")
     ap.add_argument("--verify-sub", type=int, default=8, help="--verify: poses sampled per interval")
     ap.add_argument("--verify-edge-points", type=int, default=3, help="--verify: interior points per footprint edge")
+    ap.add_argument("--rollout", action="store_true",
+                    help="roll the returned controls through the continuous dynamics (sub-stepped RK4, zero-order hold, "
+                         "open loop) and report the rolled motion's clearance, deviation and goal error (rollout.py)")
+    ap.add_argument("--rollout-substeps", type=int, default=8, help="--rollout: RK4 steps per interval")
+    ap.add_argument("--rollout-edge-points", type=int, default=3, help="--rollout: interior points per footprint edge")
     a = ap.parse_args(argv)
     run_benchmark(Path(a.config), initializer=a.initializer, weights=a.weights, results_dir=a.results, verify=a.verify,
-                  verify_sub=a.verify_sub, verify_edge_points=a.verify_edge_points)
+                  verify_sub=a.verify_sub, verify_edge_points=a.verify_edge_points, rollout=a.rollout,
+                  rollout_substeps=a.rollout_substeps, rollout_edge_points=a.rollout_edge_points)
 
 
 if __name__ == "__main__":

@@ -460,6 +460,20 @@ __device__ inline double exact_sdf(const NlotProblem& p, double x, double y) {
     return best;
 }
 
+// strict point-in-convex-polygon in the body frame: every edge cross product non-zero and of one sign (the
+// rectangle's corner order is clockwise, the triangle's counter-clockwise)
+__device__ inline bool inside_body(const NlotProblem& p, double qx, double qy) {
+    int pos = 0, neg = 0;
+    for (int i = 0; i < p.n_body; ++i) {
+        const int i1 = i + 1 < p.n_body ? i + 1 : 0;
+        const double ex = p.body[i1][0] - p.body[i][0], ey = p.body[i1][1] - p.body[i][1];
+        const double cr = ex * (qy - p.body[i][1]) - ey * (qx - p.body[i][0]);
+        pos += cr > 0.0;
+        neg += cr < 0.0;
+    }
+    return pos == p.n_body || neg == p.n_body;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Small dense symmetric indefinite LDL^T (1x1 diagonal pivoting on the largest |a_ii|).
 // Returns 0 (nneg = negative pivots) or 2 if numerically singular.  n <= NMAX compile-time.

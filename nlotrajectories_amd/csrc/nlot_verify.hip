@@ -85,20 +85,6 @@ __device__ inline void sample_pose(const double* X, int nx, int N, int sub, int 
     *th = heading ? a[2] + tau * (b[2] - a[2]) : 0.0;
 }
 
-// strict point-in-convex-polygon in the body frame: every edge cross product non-zero and of one sign (the
-// rectangle's corner order is clockwise, the triangle's counter-clockwise)
-__device__ inline bool inside_body(const NlotProblem& p, double qx, double qy) {
-    int pos = 0, neg = 0;
-    for (int i = 0; i < p.n_body; ++i) {
-        const int i1 = i + 1 < p.n_body ? i + 1 : 0;
-        const double ex = p.body[i1][0] - p.body[i][0], ey = p.body[i1][1] - p.body[i][1];
-        const double cr = ex * (qy - p.body[i][1]) - ey * (qx - p.body[i][0]);
-        pos += cr > 0.0;
-        neg += cr < 0.0;
-    }
-    return pos == p.n_body || neg == p.n_body;
-}
-
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_verify(
     const NlotProblem* __restrict__ pp, NlotVerifyOptions o, const double* __restrict__ Xall,
     const double* __restrict__ Uall, const double* __restrict__ x0, const double* __restrict__ xg,

@@ -7,6 +7,11 @@ bounds, N) is the workload's; the scene is a restated benchmark's (problem.BENCH
 the metric and stress workloads solve against a learned SDF and carry no scene of their own, so the scene is the
 caller's statement of where the trajectories are meant to drive.  Prints one JSON line: the share of the solved
 instances with flags == 0, the shares per flag, and the clearance quantiles of the solved instances.
+
+--rollout [--rollout-substeps 8] also rolls the dumped controls through the continuous dynamics (nlot_rollout_batch)
+and adds one key `rollout`: the shares per rollout flag, the quantiles of the deviation from the plan, of the goal
+error (against the plan's last knot: the dump carries no goals) and of the rolled clearance over the solved instances,
+and how many of the instances verify_batch passes the rollout flags.
 """
 import argparse
 import json
@@ -35,6 +40,8 @@ def main(argv=None):
     ap.add_argument("--workload", choices=["metric", "stress"], default="metric", help="the bench.py workload of the dump")
     ap.add_argument("--sub", type=int, default=8)
     ap.add_argument("--edge-points", type=int, default=3)
+    ap.add_argument("--rollout", action="store_true", help="also roll the controls through the dynamics (rollout_batch)")
+    ap.add_argument("--rollout-substeps", type=int, default=8)
     a = ap.parse_args(argv)
 
     from nlotrajectories_amd import _abi
@@ -57,6 +64,20 @@ def main(argv=None):
                clearance_quantiles={str(q): float(np.quantile(clearance, q)) if n else None
                                     for q in (0.0, 0.01, 0.1, 0.5, 0.9, 1.0)},
                max_defect=float(v["defect"].cpu().numpy()[solved].max()) if n else None)
+    if a.rollout:
+        from nlotrajectories_amd.rollout import rollout_batch
+
+        r = rollout_batch(prob, X, U, obstacles=scene_obstacles(a.scene), substeps=a.rollout_substeps,
+                          edge_points=a.edge_points)
+        rflags = r["flags"].cpu().numpy()[solved]
+        qs = (0.0, 0.01, 0.1, 0.5, 0.9, 1.0)
+        quant = lambda k: {str(q): float(np.nanquantile(r[k].cpu().numpy()[solved], q)) if n else None for q in qs}  # noqa: E731
+        out["rollout"] = dict(substeps=a.rollout_substeps,
+                              flag_shares={name: float(((rflags & bit) != 0).mean()) if n else None
+                                           for bit, name in _abi.ROLLOUT_FLAG_NAMES.items()},
+                              deviation_quantiles=quant("deviation"), goal_error_quantiles=quant("goal_error"),
+                              clearance_quantiles=quant("clearance"), verify_ok=int((flags == 0).sum()),
+                              verify_ok_rollout_flagged=int(((flags == 0) & (rflags != 0)).sum()))
     print(json.dumps(out))
 
 
