@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/nlot.h"
+#include "nlot_internal.h"  // NLOT_RK4_BIAS
 
 namespace nlot {
 
@@ -155,8 +156,6 @@ template <> struct Dyn<NLOT_ACKERMANN_2ND> {  // dynamics.py:121-148, output ord
 // jac / hess differentiate f_eff exactly with second-order forward jets over z = (x, u) (the oracle does the
 // same with its jets, in the same operation order).
 // ---------------------------------------------------------------------------------------------
-constexpr int NLOT_RK4_BIAS = 8;
-
 template <int N>
 struct Jt {  // value, gradient, lower-triangular Hessian over N variables
     double v, g[N], h[N * (N + 1) / 2];

@@ -11,6 +11,10 @@
 
 namespace nlot {
 
+// Dyn<D + NLOT_RK4_BIAS> (nlot_device.h) is dynamics model D with RK4 defects; the solver, the verifier and the
+// rollout dispatch on dynamics + (integrator == NLOT_INTEG_RK4 ? NLOT_RK4_BIAS : 0)
+constexpr int NLOT_RK4_BIAS = 8;
+
 // thread-local last error (nlot_last_error)
 void set_error(const std::string& msg);
 

@@ -36,17 +36,9 @@
 
 #include "nlot_device.h"
 #include "nlot_internal.h"
+#include "nlot_solver_ws.h"
 
 namespace nlot {
-
-// PH_SOFT1 / PH_SOFT2: IPOPT's soft restoration step (BacktrackingLineSearch::TrySoftRestoStep) — the damped
-// step's filter test on a value launch, then (not filter-acceptable) the primal-dual error at the tentatively
-// accepted point on a full launch.  PH_RINIT: first step of a feasibility restoration phase (its point's full
-// evaluation, then MinC_1NrmRestorationPhase's initialisation); while SC_RESTO = 1 the EVAL / LS phases belong to
-// the restoration problem (k_resto_a / k_ric<DYN, true> / k_resto_b / k_resto_ls).
-enum Phase { PH_INIT = 0, PH_EVAL = 1, PH_LS = 2, PH_DONE = 3, PH_SOC = 4, PH_SOFT1 = 5, PH_SOFT2 = 6, PH_RINIT = 7 };
-// k_iter_a's passes (run() launches SOC on the side stream at the start of a step and EVAL after the full MLP launch)
-enum IterPass { PASS_ALL = 0, PASS_INIT = 1, PASS_SOC = 2, PASS_EVAL = 3 };
 
 // Minimum waves per SIMD the per-instance kernels are compiled for (register budget 512 / w per lane),
 // and the depth of k_ric's stage ring (its LDS per wavefront sets k_ric's occupancy).  These kernels wait
@@ -83,255 +75,6 @@ enum IterPass { PASS_ALL = 0, PASS_INIT = 1, PASS_SOC = 2, PASS_EVAL = 3 };
 #if !defined(NLOT_RIC_FENCED) && !defined(NLOT_RIC_INORDER)
 #define NLOT_RIC_INORDER
 #endif
-enum Scal {
-    SC_MU, SC_TAU, SC_DWLAST, SC_THMAX, SC_THMIN, SC_ALPHA, SC_AMAX, SC_AMIN, SC_AZ, SC_THETA, SC_PHI, SC_GD,
-    SC_DW, SC_DC, SC_STATUS, SC_ITERS, SC_PHASE, SC_TRIALS, SC_NFILT, SC_RANK, SC_E0, SC_NCAND,
-    SC_FREE, SC_MUMAX, SC_NAF,  // adaptive mu: free-mode flag, mu_max, progress-filter entries
-    // hand-off k_iter_a -> k_ric -> k_iter_b: Newton-solve state (0 idle, 1 pending, 2 solved, 3 LSQ
-    // failed), its barrier parameters and right-hand-side count, and the optimality scalars the
-    // quality-function oracle needs
-    SC_RIC, SC_RMU0, SC_RMU1, SC_RNR, SC_USEQF, SC_AVG, SC_DSQ, SC_PSQ, SC_NZC,
-    SC_ACCSLOT,  // trial-list slot of the accepted line-search candidate (forward reuse), -1 if none
-    // IPOPT's globalisation safeguards: second-order correction (count in progress, the
-    // original trial's alpha and alpha_z, theta of the last corrected trial), k_ric's fixed delta_w (-1: the
-    // inertia-correction loop), watchdog (active, shortened-step counter, trials, reference values and the
-    // saved line-search scalars), tiny step (this iteration, the previous one), max primal infeasibility
-    SC_SOCK, SC_SOCA, SC_SOCAZ, SC_SOCTH, SC_RICFIX,
-    SC_WD, SC_WDSHORT, SC_WDTRIAL, SC_WDTH, SC_WDPH, SC_WDGD, SC_WDAT, SC_WDAZ, SC_WDAMIN, SC_WDMU, SC_WDTAU,
-    SC_TINY, SC_TINYLAST, SC_PRIMAL,
-    // IPOPT's filter reset heuristic: last rejection of this line search was by the filter, successive such
-    // iterations, resets done
-    SC_LASTREJF, SC_NFREJ, SC_NFRES,
-    // soft restoration: active, iterations, primal-dual error at the current point and the mu it was taken at
-    SC_INSOFT, SC_SOFTCNT, SC_PDC, SC_MUPD,
-    // feasibility restoration (MinC_1Nrm): active, first iteration, the original problem's mu / tau / last
-    // delta_w, theta_R and phi_R at the restoration's start, rho, zeta, the restoration's theta_max / theta_min
-    // and filter entries, restoration phases started (statistics)
-    SC_RESTO, SC_RFIRST, SC_RMUO, SC_RTAUO, SC_RDWO, SC_THR, SC_PHR, SC_RHO, SC_ZETA, SC_RTHMAX, SC_RTHMIN,
-    SC_RNFILT, SC_NRESTO,
-    // inertia correction carried over to the next global step (k_ric's attempt cap): the next delta_w to try (-1:
-    // none pending) and the delta_w already added into hg
-    SC_RETRY, SC_DWHG,
-    SC_COUNT
-};
-// Filters (line search, adaptive-mu progress, restoration): IPOPT's Filter is an unbounded list from which
-// dominated entries are removed.  At most one entry enters per iteration (the line-search filter can grow to
-// 2 max_iter + O(1) in principle); the largest size measured over the round-4 metric bench was 613 (bench.py
-// config.filters), so 1024 entries per filter are unbounded in effect there.  An overflow forgets the oldest entry;
-// it is counted (NlotSolveStats.filter_forgotten, the restoration filter included) and reported by bench.py.
-constexpr int FILT_MAX = 1024;
-// ints per step-parity counter set (workspace counters: 2 sets): [0..8) the phase machine's counts (Ws::cnt), [8..11)
-// diagnostics of the factorising Newton solves (attempts summed, their maximum, solves needing more than one), [11]
-// the largest filter size reached and [12] filter entries forgotten at capacity (diagnostics), [15] the most
-// factorisations one restoration Newton solve took (diagnostics), [13]
-// where k_admit's slots start in the active list.  After the two sets: the free-slot count and k_admit's error flag.
-constexpr int CSET = 16;
-constexpr int NSPEC = 8;  // step lengths evaluated per line-search round after a first rejection
-constexpr int MMAX = 4;  // inequalities per knot (rectangle without slack)
-
-struct Dims {
-    int N, nx, nu, ns, M, nc, nb, nv, sd;  // nv = nu + ns (stage k < N)
-    int tidx[8];
-    int ppk;  // SDF points per knot (corners, or 1 for a dot)
-    // general bounds (NlotSolverOptions.general_bounds): the control bounds and slack >= 0 as constraint rows, the way
-    // CasADi's Opti hands them to IPOPT (runner.py:67-69,101-103).  ngb = bound rows N nu + ns (N + 1) (the workspace
-    // always holds their arrays: the workspace size does not depend on the options); gcb = 1 selects the form
-    int ngb, gcb;
-};
-
-static Dims make_dims(const NlotProblem& p) {
-    Dims d{};
-    d.N = p.N;
-    d.nx = p.nx;
-    d.nu = p.nu;
-    d.ns = p.use_slack ? 1 : 0;
-    d.nb = p.shape == NLOT_SHAPE_DOT ? 1 : p.n_body;
-    d.M = p.shape == NLOT_SHAPE_DOT ? 1 : (p.use_slack ? 1 : p.n_body);
-    d.sd = (p.shape == NLOT_SHAPE_POLYGON && p.use_slack) ? 1 : 0;
-    d.nv = p.nu + d.ns;
-    d.nc = 0;
-    for (int i = 0; i < p.nx; ++i)
-        if (p.enforce_heading || i != 2) d.tidx[d.nc++] = i;
-    d.ppk = d.nb;
-    d.ngb = p.N * p.nu + d.ns * (p.N + 1);
-    d.gcb = 0;  // run() sets it from the options
-    return d;
-}
-
-// Riccati storage per knot (one Newton solve with up to two right-hand sides):
-//   slot (LDS when it fits, else HBM): [A B 0] (nx x nz) | c | M (2x2) | K (nv x nx) | k (2 x nv) | Kn (nv x nc)
-//     — everything the sequential forward sweep reads;
-//   hg (HBM): H (nz x nz) | g (2 x nz) — built in parallel over knots, read once by the backward sweep
-//     (prefetched one stage ahead);
-//   vf (HBM): P (nx x nx) | p (2 x nx) | Gamma (nx x nc) — written by the backward sweep, read by the
-//     parallel multiplier pass.  (nz = nx + nu + 1, nv = nu + 1, nc = nx.)
-//   Layouts (row-major, ncol = nx + 2 + nc gain columns K | k_0 | k_1 | Kn):
-//     slot = [A B 0 | c | pad] (nx x ab_row) | M | GN (ncol x nv);  hg = [H | g_0 g_1] (nz x (nz+2)) (the
-//     Riccati lane of column j reads row j, H being symmetric, or a g column top to bottom);
-//     vf = [P | p_0 p_1 | Gamma] (nx x ncol).
-__host__ __device__ constexpr int ab_row(int nx, int nu) { return (nx + nu + 2 + 1) & ~1; }  // [A B 0 | c], even
-__host__ __device__ constexpr int slot_len(int nx, int nu) {
-    return nx * ab_row(nx, nu) + 4 + (nx + 2 + nx) * (nu + 1);
-}
-__host__ __device__ constexpr int hg_len(int nx, int nu) { return (nx + nu + 1) * (nx + nu + 3); }
-__host__ __device__ constexpr int vf_len(int nx, int nu) { return nx * (nx + 2 + nx); }
-// quality-function oracle step buffers (affine / centering): dX dU dS yi yk yt | dT dzl dzu dzs dvt | dsb (the
-// bound rows' slack step, general bounds)
-__host__ __device__ constexpr int qf_len(int N, int nx, int nu, int M, int ngb) {
-    return (N + 1) * nx + N * nu + (N + 1) + nx + N * nx + 8 + (N + 1) * M + 2 * N * nu + (N + 1) + (N + 1) * M + ngb;
-}
-
-// an iterate (X U S T yi yk yt yd zl zu zs vt sb yb) or a step (dX dU dS dT yi_n yk_n yt_n yd_n dzl dzu dzs dvt dsb
-// yb_n): the save areas of the second-order correction and the watchdog
-__host__ __device__ constexpr int it_len(int N, int nx, int nu, int M, int ngb) {
-    return (N + 1) * nx + 3 * N * nu + 2 * (N + 1) + 3 * (N + 1) * M + nx + N * nx + 8 + 2 * ngb;
-}
-
-// restoration rows (oracle Sol::rp ...): [initial state nx][dynamics N nx][terminal nc][inequalities (N+1) M]
-// [bound rows ngb (general bounds)], allocated with the terminal block padded to 8
-__host__ __device__ constexpr int ne_len(int N, int nx, int M, int ngb) { return nx + N * nx + 8 + (N + 1) * M + ngb; }
-
-// a stored pivoted LDL^T factor of an n x n block (ldl_factor's in-place form, then the permutation): the Q_vv
-// factor of every stage and the terminal block's, kept by each Newton solve for the second-order corrections
-__host__ __device__ constexpr int ldl_len(int n) { return n * n + n; }
-
-// instance-major arrays: (name, per-instance length)
-#define NLOT_WS_ARRAYS(X_)                                                                             \
-    X_(X, (N + 1) * nx) X_(U, N * nu) X_(S, N + 1) X_(T, (N + 1) * M) X_(yi, nx) X_(yk, N * nx) X_(yt, 8) \
-    X_(yd, (N + 1) * M) X_(zl, N * nu) X_(zu, N * nu) X_(zs, N + 1) X_(vt, (N + 1) * M)                \
-    X_(dv, (N + 1) * M) X_(Jd, (N + 1) * M * 3) X_(Hd, (N + 1) * 6) X_(rci, nx) X_(rcd, N * nx)         \
-    X_(rct, 8) X_(rcq, (N + 1) * M) X_(dX, (N + 1) * nx) X_(dU, N * nu) X_(dS, N + 1)                  \
-    X_(dT, (N + 1) * M) X_(yi_n, nx) X_(yk_n, N * nx) X_(yt_n, 8) X_(yd_n, (N + 1) * M)                \
-    X_(dzl, N * nu) X_(dzu, N * nu) X_(dzs, N + 1) X_(dvt, (N + 1) * M) X_(sc, SC_COUNT)               \
-    X_(filt, 2 * FILT_MAX) X_(afilt, 2 * FILT_MAX) X_(qa, qf_len(N, nx, nu, M, ngb)) X_(qc, qf_len(N, nx, nu, M, ngb)) \
-    X_(stg, (N + 1) * slot_len(nx, nu)) X_(hg, (N + 1) * hg_len(nx, nu)) X_(vf, (N + 1) * vf_len(nx, nu))   \
-    X_(dX2, (N + 1) * nx) X_(dU2, N * nu) X_(dS2, N + 1) X_(yi2, nx) X_(yk2, N * nx) X_(yt2, 8)         \
-    X_(sts, it_len(N, nx, nu, M, ngb)) X_(rcs, nx + N * nx + 8 + (N + 1) * M + ngb)                     \
-    X_(wdi, it_len(N, nx, nu, M, ngb)) X_(wdd, it_len(N, nx, nu, M, ngb))                               \
-    X_(rp, ne_len(N, nx, M, ngb)) X_(rn, ne_len(N, nx, M, ngb)) X_(rzp, ne_len(N, nx, M, ngb))           \
-    X_(rzn, ne_len(N, nx, M, ngb)) X_(rdp, ne_len(N, nx, M, ngb)) X_(rdn, ne_len(N, nx, M, ngb))         \
-    X_(rdzp, ne_len(N, nx, M, ngb)) X_(rdzn, ne_len(N, nx, M, ngb)) X_(dsoft, ne_len(N, nx, M, ngb))     \
-    X_(esoft, ne_len(N, nx, M, ngb)) X_(rfilt, 2 * FILT_MAX)                                            \
-    X_(qfac, (N + 1) * ldl_len(nu + 1)) X_(tfac, ldl_len(nx)) X_(x0s, nx) X_(xgs, nx) X_(phi, N * nx * (nx + 2)) \
-    X_(sb, ngb) X_(yb, ngb) X_(rcb, ngb) X_(dsb, ngb) X_(yb_n, ngb)
-
-struct Ws {
-#define NLOT_DECL(name, cnt) \
-    double* name;            \
-    int L_##name;
-    NLOT_WS_ARRAYS(NLOT_DECL)
-#undef NLOT_DECL
-    float* pts;  // compacted corner list, rank-major [rank][P][2]
-    float* mo;   // MLP outputs [6][cap * P] (rank-major within a plane)
-    // trial lists by global-step parity q: the full launch of step s + 1 reuses step s's accepted
-    // candidate while k_accept of step s already emits the candidates of step s + 1
-    float* tpts[2];      // trial corner list [slot][P][2] (slot = rank + candidate), cap * NSPEC slots
-    float* tval[2];      // its values [slot][P]
-    uint32_t* tmask[2];  // its hidden-layer ReLU patterns [4][slot][P]
-    int* tsrc;           // per evaluation rank: trial slot whose forward the full launch may reuse, or -1
-    int* cnt;  // counters of step parity q at cnt + CSET q: [0] evaluation ranks, [1] trial slots, [2] next active
-               // count, [3] full-launch points whose forward was reused, [4] Newton solves, [5] restoration list count,
-               // [6] second-order corrections, [7] restoration Newton solves
-    int* act[2]; // active instance lists (ping-pong)
-    int* actr[2]; // the instances of act in a restoration phase (count: counter [5] of the step's set)
-    int* ricl;    // this step's factorising Newton solves (count: counter [4]), compacted by k_iter_a for k_ric
-    int* socl;    // this step's second-order corrections (count: counter [6])
-    // Slots: every array above is indexed by slot (cap slots); sinst[slot] is the instance a slot holds.  An instance
-    // leaving the active list (k_accept) writes its outputs (o*, instance-indexed, caller-owned) and frees its slot
-    // (freel, count at cnt[2 CSET]); k_admit gives free slots to the next instances, k_init_state starts them.
-    int* sinst;
-    int* freel;
-    double *oX, *oU, *oS, *ocost;
-    int32_t *ostat, *oiters;
-    int64_t cap;
-    int ppk;
-    int prio;  // NLOT_SETPRIO: the side-stream chains (restoration solves, corrections) raise their waves' issue priority
-};
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// doubles of all instance-major arrays for B instances, each array rounded up to 256 bytes
-static size_t ws_doubles(const Dims& d, int64_t B) {
-    const int N = d.N, nx = d.nx, nu = d.nu, M = d.M, ngb = d.ngb;
-    size_t n = 0;
-#define NLOT_CNT(name, cnt) n += ((size_t)(cnt) * (size_t)B + 31) & ~(size_t)31;
-    NLOT_WS_ARRAYS(NLOT_CNT)
-#undef NLOT_CNT
-    return n;
-}
-
-constexpr size_t kHdr = 32768;  // device copies of NlotProblem, Dims, Ws (kernels read them through pointers:
-                                // a by-value struct argument indexed at run time is copied to scratch)
-constexpr size_t kHdrProblem = 0, kHdrDims = 24576, kHdrWs = 28672;  // NlotProblem ~14.5 KB (vertex pool)
-
-static size_t ws_bytes(const Dims& d, int64_t B, bool mlp) {
-    size_t b = kHdr + align256(ws_doubles(d, B) * sizeof(double));
-    if (mlp) {  // corner list and outputs sized for NSPEC line-search candidates per instance
-        const size_t P = (size_t)d.ppk * (d.N + 1);
-        b += align256(P * (size_t)B * NSPEC * 2 * sizeof(float));
-        b += align256(6 * P * (size_t)B * NSPEC * sizeof(float));
-        b += 2 * align256(P * (size_t)B * NSPEC * 2 * sizeof(float));     // tpts, per step parity
-        b += 2 * align256(P * (size_t)B * NSPEC * sizeof(float));         // tval
-        b += 2 * align256(4 * P * (size_t)B * NSPEC * sizeof(uint32_t));  // tmask
-        b += align256((size_t)B * sizeof(int));                    // tsrc
-    }
-    b += align256(2 * (size_t)B * sizeof(int));
-    b += align256(2 * (size_t)B * sizeof(int));  // restoration lists
-    b += 2 * align256((size_t)B * sizeof(int));  // Newton-solve and correction lists
-    b += 2 * align256((size_t)B * sizeof(int));  // slot -> instance, free slots
-    b += 256;  // counters (2 sets of CSET ints)
-    return b;
-}
-
-static Ws carve(const Dims& d, int64_t B, bool mlp, void* base) {
-    Ws w{};
-    w.cap = B;
-    w.ppk = d.ppk;
-    const int N = d.N, nx = d.nx, nu = d.nu, M = d.M, ngb = d.ngb;
-    base = (char*)base + kHdr;
-    double* q = (double*)base;
-#define NLOT_TAKE(name, cnt)          \
-    w.name = q;                       \
-    w.L_##name = (int)(cnt);          \
-    q += ((size_t)(cnt) * (size_t)B + 31) & ~(size_t)31;
-    NLOT_WS_ARRAYS(NLOT_TAKE)
-#undef NLOT_TAKE
-    char* c = (char*)base + align256(ws_doubles(d, B) * sizeof(double));
-    if (mlp) {
-        const size_t P = (size_t)d.ppk * (N + 1);
-        w.pts = (float*)c;
-        c += align256(P * (size_t)B * NSPEC * 2 * sizeof(float));
-        w.mo = (float*)c;
-        c += align256(6 * P * (size_t)B * NSPEC * sizeof(float));
-        for (int q = 0; q < 2; ++q) {
-            w.tpts[q] = (float*)c;
-            c += align256(P * (size_t)B * NSPEC * 2 * sizeof(float));
-            w.tval[q] = (float*)c;
-            c += align256(P * (size_t)B * NSPEC * sizeof(float));
-            w.tmask[q] = (uint32_t*)c;
-            c += align256(4 * P * (size_t)B * NSPEC * sizeof(uint32_t));
-        }
-        w.tsrc = (int*)c;
-        c += align256((size_t)B * sizeof(int));
-    }
-    w.act[0] = (int*)c;
-    w.act[1] = (int*)c + B;
-    c += align256(2 * (size_t)B * sizeof(int));
-    w.actr[0] = (int*)c;
-    w.actr[1] = (int*)c + B;
-    c += align256(2 * (size_t)B * sizeof(int));
-    w.ricl = (int*)c;
-    c += align256((size_t)B * sizeof(int));
-    w.socl = (int*)c;
-    c += align256((size_t)B * sizeof(int));
-    w.sinst = (int*)c;
-    c += align256((size_t)B * sizeof(int));
-    w.freel = (int*)c;
-    c += align256((size_t)B * sizeof(int));
-    w.cnt = (int*)c;
-    return w;
-}
-
 // element i of instance b's array (instance-major)
 #define AT(arr, i) (ws.arr[(size_t)b * ws.L_##arr + (i)])
 #define SC(i) AT(sc, i)
@@ -5081,626 +4824,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NLOT_WPE_RLS
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// host driver
-// ---------------------------------------------------------------------------------------------
-// Per-dynamics compile units (Makefile): NLOT_UNIT = D >= 0 instantiates run<D> and run<D + NLOT_RK4_BIAS> only;
-// NLOT_UNIT = -1 holds the C ABI, the statistics and the dispatch; without NLOT_UNIT (tuning builds) one unit does all.
-#ifndef NLOT_UNIT
-static thread_local NlotSolveStats g_stats;
-static int g_timing = 0;  // nlot_set_timing: 0 off; k: one step in each group of k, at position (step / k) % k (rotating)
-#else
-extern thread_local NlotSolveStats g_stats;
-extern int g_timing;
-#if NLOT_UNIT < 0
-thread_local NlotSolveStats g_stats;
-int g_timing = 0;
-#endif
-#endif
 
-static int validate(const NlotProblem* p, const NlotSolverOptions* o, const NlotMlp* mlp, int64_t B) {
-    if (!p || !o) { set_error("null problem/options"); return NLOT_ERR_INVALID; }
-    static const int NXS[6] = {4, 4, 3, 5, 4, 7};
-    if (p->dynamics < 0 || p->dynamics > 5 || p->nx != NXS[p->dynamics] || p->nu != 2) {
-        set_error("dynamics / nx / nu mismatch");
-        return NLOT_ERR_INVALID;
-    }
-    if (p->N < 2 || p->N > 4096 || p->dt <= 0) { set_error("N must be in [2, 4096], dt > 0"); return NLOT_ERR_INVALID; }
-    if (o->general_bounds != 0 && o->general_bounds != 1) {
-        set_error("general_bounds: 0 variable bounds, 1 constraint rows (CasADi Opti's form)");
-        return NLOT_ERR_INVALID;
-    }
-    if (p->integrator != NLOT_INTEG_EULER && p->integrator != NLOT_INTEG_RK4) {
-        set_error("integrator must be NLOT_INTEG_EULER or NLOT_INTEG_RK4"); return NLOT_ERR_INVALID;
-    }
-    if (p->shape == NLOT_SHAPE_POLYGON && (p->n_body < 1 || p->n_body > MMAX)) {
-        set_error("polygon footprint: 1..4 corners"); return NLOT_ERR_INVALID;
-    }
-    if (p->shape == NLOT_SHAPE_POLYGON && p->nx < 3) { set_error("polygon footprint needs a heading state"); return NLOT_ERR_INVALID; }
-    if (p->sdf_kind == NLOT_SDF_MLP && !mlp) { set_error("learned SDF requires an NlotMlp"); return NLOT_ERR_INVALID; }
-    if (p->sdf_kind == NLOT_SDF_ANALYTIC && (p->n_obs < 1 || p->n_obs > NLOT_MAX_OBS)) {
-        set_error("analytic SDF needs 1..NLOT_MAX_OBS (128) obstacles"); return NLOT_ERR_INVALID;
-    }
-    if (p->sdf_kind == NLOT_SDF_ANALYTIC) {
-        if (p->n_verts < 0 || p->n_verts > NLOT_MAX_VERTS) { set_error("n_verts out of range"); return NLOT_ERR_INVALID; }
-        for (int i = 0; i < p->n_obs; ++i) {
-            const NlotObstacle& q = p->obs[i];
-            if (q.type < NLOT_OBS_CIRCLE || q.type > NLOT_OBS_TRAPEZOID) { set_error("unknown obstacle type"); return NLOT_ERR_INVALID; }
-            const bool poly = q.type == NLOT_OBS_POLYGON || q.type == NLOT_OBS_TRAPEZOID;
-            if (poly && (q.nv < (q.type == NLOT_OBS_TRAPEZOID ? 4 : 2) || (q.type == NLOT_OBS_TRAPEZOID && q.nv != 4) ||
-                         q.v0 < 0 || q.v0 + q.nv > p->n_verts)) {
-                set_error("polygon / trapezoid obstacle: vertex range outside verts[0, n_verts) (a trapezoid has 4)");
-                return NLOT_ERR_INVALID;
-            }
-        }
-    }
-    for (int i = 0; i < p->nu; ++i)
-        if (!(p->umin[i] < p->umax[i])) { set_error("control bounds must satisfy min < max"); return NLOT_ERR_INVALID; }
-    if (o->max_iter < 0 || o->max_iter > 10000000) { set_error("max_iter must be in [0, 1e7]"); return NLOT_ERR_INVALID; }
-    if (o->resto && (o->resto_penalty_parameter <= 0 || o->required_infeasibility_reduction <= 0 ||
-                     o->required_infeasibility_reduction >= 1 || o->resto_proximity_weight < 0)) {
-        set_error("restoration options: rho > 0, 0 < kappa_resto < 1, proximity weight >= 0");
-        return NLOT_ERR_INVALID;
-    }
-    if (o->max_soc < 0 || o->watchdog_shortened_iter_trigger < 0 || o->watchdog_trial_iter_max < 0) {
-        set_error("max_soc / watchdog options must be >= 0");
-        return NLOT_ERR_INVALID;
-    }
-    if (o->mu_strategy != 0 && o->mu_strategy != 1) { set_error("mu_strategy: 0 monotone, 1 adaptive"); return NLOT_ERR_INVALID; }
-    if (B <= 0 || B > (int64_t)1 << 26) { set_error("B out of range"); return NLOT_ERR_INVALID; }
-    return NLOT_OK;
-}
+}  // namespace nlot
 
-template <int DYN>
-int run(const NlotProblem& p, const NlotSolverOptions& o, const NlotMlp* mlp, const double* x0, const double* xg,
-               const double* Xinit, double* X, double* U, double* S, double* cost, int32_t* status, int32_t* iters,
-               int64_t B, void* workspace, hipStream_t st) {
-    Dims dm = make_dims(p);
-    dm.gcb = o.general_bounds ? 1 : 0;
-    const bool use_mlp = p.sdf_kind == NLOT_SDF_MLP;
-    // slots: min(B, max_active) (continuous batching) or B; the workspace holds the slots' state only
-    const int cap_slots = (int)(o.max_active > 0 && o.max_active < B ? o.max_active : B);
-    Ws ws = carve(dm, cap_slots, use_mlp, workspace);
-    ws.oX = X;
-    ws.oU = U;
-    ws.oS = S;
-    ws.ocost = cost;
-    ws.ostat = status;
-    ws.oiters = iters;
-    ws.prio = getenv("NLOT_SETPRIO") ? atoi(getenv("NLOT_SETPRIO")) : 0;
-    NlotProblem* dP = (NlotProblem*)((char*)workspace + kHdrProblem);
-    Dims* dD = (Dims*)((char*)workspace + kHdrDims);
-    Ws* dW = (Ws*)((char*)workspace + kHdrWs);
-    static_assert(sizeof(NlotProblem) <= kHdrDims - kHdrProblem && sizeof(Dims) <= kHdrWs - kHdrDims &&
-                  sizeof(Ws) <= kHdr - kHdrWs, "workspace header");
-    NLOT_HIP_CHECK(hipMemcpyAsync(dP, &p, sizeof(NlotProblem), hipMemcpyHostToDevice, st));
-    NLOT_HIP_CHECK(hipMemcpyAsync(dD, &dm, sizeof(Dims), hipMemcpyHostToDevice, st));
-    NLOT_HIP_CHECK(hipMemcpyAsync(dW, &ws, sizeof(Ws), hipMemcpyHostToDevice, st));
-    const int Bi = (int)B;
-    const int64_t P = (int64_t)dm.ppk * (dm.N + 1);
-    g_stats = NlotSolveStats{};
-    g_stats.filter_capacity = FILT_MAX;
-    hipLaunchKernelGGL(k_init_state, dim3(cap_slots), dim3(64), 0, st, dP, dD, o, ws, x0, xg, Xinit, nullptr, nullptr);
-    NLOT_HIP_CHECK(hipGetLastError());
-    // Steps run ahead of the host: every kernel reads its step's active count on the device (cnt[2] of the
-    // step's counter set, written by the previous step's k_accept), and grids are sized by the host's last
-    // known count, an upper bound (the active set only shrinks).  The host waits once per KPIPE steps: it
-    // then learns the counts (the D2H copies of each step's counters land in a pinned ring) and whether any
-    // instance is still active; the at most KPIPE - 1 steps launched past the end exit at once.
-    constexpr int KPIPE = 8;
-    // host-side resources released on every return path (NLOT_HIP_CHECK returns early)
-    struct Res {
-        int* hcnt = nullptr;
-        hipEvent_t ev[KPIPE][10] = {};  // [8], [9]: the early value launch (NLOT_EARLY_VALUE) on its stream
-        hipEvent_t noev[10] = {};       // the untimed steps' (no events)
-        bool timed[KPIPE] = {};         // the ring slot's step was timed
-        hipStream_t s2 = nullptr, s3 = nullptr, s4 = nullptr;       // side streams: SOC / restoration / early values
-        hipEvent_t e_a = nullptr, e_soc = nullptr, e_r = nullptr, e_s = nullptr, e_v0 = nullptr, e_v1 = nullptr;
-        ~Res() {
-            for (auto& r : ev)
-                for (auto& e : r)
-                    if (e) (void)hipEventDestroy(e);
-            for (hipEvent_t e : {e_a, e_soc, e_r, e_s, e_v0, e_v1})
-                if (e) (void)hipEventDestroy(e);
-            if (s2) (void)hipStreamDestroy(s2);
-            if (s3) (void)hipStreamDestroy(s3);
-            if (s4) (void)hipStreamDestroy(s4);
-            if (hcnt) (void)hipHostFree(hcnt);
-        }
-    } res;
-    // + 2: the free-slot count and k_admit's error flag, read at every synchronisation
-    NLOT_HIP_CHECK(hipHostMalloc((void**)&res.hcnt, (KPIPE * 2 * CSET + 2) * sizeof(int),
-                                 hipHostMallocMapped | hipHostMallocCoherent));
-    // The second-order corrections (substitution, short) and the restoration instances' Newton solves (a longer
-    // sequential sweep, few instances) touch disjoint instances from the main Newton solve: they run on a side
-    // stream, forked after k_iter_a, so their latency hides under k_ric's; k_iter_b joins the corrections, the
-    // value-MLP launch joins the restoration chain (k_resto_b appends to the same trial list).
-    // NLOT_STREAM_PRIO (A/B knob, measured neutral in round 4): 1 = the restoration stream at the highest priority,
-    // 2 = the correction stream too; unset: default-priority streams
-    int stream_prio = 0;
-    if (const char* e = getenv("NLOT_STREAM_PRIO")) stream_prio = atoi(e);
-    if (stream_prio > 0) {
-        int prio_least = 0, prio_greatest = 0;
-        NLOT_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-        if (stream_prio >= 2) NLOT_HIP_CHECK(hipStreamCreateWithPriority(&res.s2, hipStreamNonBlocking, prio_greatest));
-        else NLOT_HIP_CHECK(hipStreamCreateWithFlags(&res.s2, hipStreamNonBlocking));
-        NLOT_HIP_CHECK(hipStreamCreateWithPriority(&res.s3, hipStreamNonBlocking, prio_greatest));
-    } else {
-        NLOT_HIP_CHECK(hipStreamCreateWithFlags(&res.s2, hipStreamNonBlocking));
-        NLOT_HIP_CHECK(hipStreamCreateWithFlags(&res.s3, hipStreamNonBlocking));
-    }
-    NLOT_HIP_CHECK(hipEventCreateWithFlags(&res.e_a, hipEventDisableTiming));
-    NLOT_HIP_CHECK(hipEventCreateWithFlags(&res.e_soc, hipEventDisableTiming));
-    NLOT_HIP_CHECK(hipEventCreateWithFlags(&res.e_r, hipEventDisableTiming));
-    NLOT_HIP_CHECK(hipEventCreateWithFlags(&res.e_s, hipEventDisableTiming));
-    NLOT_HIP_CHECK(hipEventCreateWithFlags(&res.e_v0, hipEventDisableTiming));
-    NLOT_HIP_CHECK(hipEventCreateWithFlags(&res.e_v1, hipEventDisableTiming));
-    NLOT_HIP_CHECK(hipStreamCreateWithFlags(&res.s4, hipStreamNonBlocking));
-    hipStream_t s2 = res.s2, s3 = res.s3, s4 = res.s4;
-    // stream layout of the step (A/B knobs NLOT_SOC_FORK, NLOT_EARLY_VALUE).  The early value launch (the previous
-    // step's line-search candidates evaluated on a fourth stream while this step's evaluations and Newton solves run)
-    // is on by default since round 4: +1.3 % at the bench's scheduling with the round-4 MLP kernels (bitwise-equal
-    // results, scripts/gpu_r04q.sh; neutral in round 3 when the full MLP launch held one 512-VGPR wave per SIMD)
-    int soc_fork = 0, early_value = 1;
-    if (const char* e = getenv("NLOT_SOC_FORK")) soc_fork = std::max(0, std::min(2, atoi(e)));
-    if (const char* e = getenv("NLOT_EARLY_VALUE")) early_value = atoi(e) != 0;
-    const int t_every = g_timing;
-    g_stats.timing_every = t_every;
-    if (t_every)
-        for (int k = 0; k < KPIPE; ++k)
-            for (int i = 0; i < 10; ++i) NLOT_HIP_CHECK(hipEventCreate(&res.ev[k][i]));
-    MlpOut mo{}, mo_t[2] = {};
-    MlpReuse reuse[2] = {};
-    if (use_mlp) {
-        const int64_t plane = P * (int64_t)cap_slots * NSPEC;  // the MLP output planes hold the slots' points
-        mo.val = ws.mo; mo.gx = ws.mo + plane; mo.gy = ws.mo + 2 * plane; mo.hxx = ws.mo + 3 * plane;
-        mo.hxy = ws.mo + 4 * plane; mo.hyx = mo.hxy; mo.hyy = ws.mo + 5 * plane;
-        mo.sv = mo.sg = mo.sh = 1;
-        // trial lists (by step parity): values + ReLU patterns, reused by the next full launch at the
-        // accepted point
-        static const bool no_reuse = getenv("NLOT_MLP_REUSE") && strcmp(getenv("NLOT_MLP_REUSE"), "0") == 0;
-        for (int q = 0; q < 2; ++q) {
-            mo_t[q].val = ws.tval[q];
-            mo_t[q].sv = 1;
-            mo_t[q].mask = ws.tmask[q];
-            mo_t[q].mask_plane = plane;
-            reuse[q] = MlpReuse{no_reuse ? nullptr : ws.tsrc, ws.tpts[q], ws.tval[q], ws.tmask[q], plane, nullptr};
-        }
-    }
-    g_stats.slots_in_lds = 0;  // stage slots live in the HBM workspace; k_ric stages them through LDS
-    const int ric_blocks_per = RicG<DYN>::IPW;
-    // speculation while one value launch stays below ~56 GFLOP of forward work: 8192 instances of the metric
-    // (P = 204 corners x 33,536 FLOP; measured best of {512, 2048, 8192} x {1, 2} at B = 65536), 138 of the
-    // stress config (P = 1028 x 394,752 FLOP)
-    int spec_threshold = 8192, spec_bulk = 2;  // 2 step lengths per later round in the bulk: -1.5 % (r03 ab8)
-    if (use_mlp) {
-        const double H = mlp->dev.H, fwd = 2.0 * (2.0 * H + mlp->dev.n_hidden * H * H + H);
-        spec_threshold = (int)std::max(1.0, std::min(1e9, 5.6e10 / (fwd * (double)P)));
-    }
-    if (const char* e = getenv("NLOT_SPEC_THRESHOLD")) spec_threshold = atoi(e);
-    if (const char* e = getenv("NLOT_SPEC_BULK")) spec_bulk = std::max(1, std::min(NSPEC, atoi(e)));
-    // k_ric's inertia-correction attempts per launch while more than ric_tries_min instances are active (the rest of
-    // an instance's delta_w sequence continues in the next step's launch)
-    // (round 5, after the restoration solves joined the cap: at every batch size, +0.8 % metric, +4.9 % benchmark 6,
-    // profiles/r05/ab_tries_min_r05az.log; the results do not depend on it)
-    int ric_tries = 1, ric_tries_min = 0;
-    if (const char* e = getenv("NLOT_RIC_TRIES")) ric_tries = std::max(1, atoi(e));
-    if (const char* e = getenv("NLOT_RIC_TRIES_MIN")) ric_tries_min = atoi(e);
-    // the same cap for the restoration solves (side stream; NLOT_RESTO_TRIES=0: every attempt in one launch)
-    bool resto_tries = true;
-    if (const char* e = getenv("NLOT_RESTO_TRIES")) resto_tries = atoi(e) != 0;
-    double progress_s = 0, t_prog = 0;
-    if (const char* e = getenv("NLOT_PROGRESS")) progress_s = atof(e);
-    t_prog = progress_s;
-    const auto t_prog0 = std::chrono::steady_clock::now();
-    int kpipe = KPIPE;
-    if (const char* e = getenv("NLOT_PIPE")) kpipe = std::max(1, std::min(KPIPE, atoi(e)));
-    // a safety net against a phase-machine bug, not an iteration limit (max_iter bounds every instance): at most
-    // 64 global steps per iteration per admission wave
-    const int64_t waves = (B + std::max(1, o.max_active > 0 && o.max_active < Bi ? o.max_active : Bi) - 1) /
-                          std::max(1, o.max_active > 0 && o.max_active < Bi ? o.max_active : Bi);
-    const int64_t max_steps = ((int64_t)o.max_iter + 2) * 64 * (waves + 1);
-    // Continuous batching (o.max_active = capacity < B): the first `capacity` instances start; whenever a host
-    // synchronisation finds at least capacity / 32 slots free, the next instances (index order) join the active
-    // list and run their INIT step (corners, slack push, least-squares multipliers) in the next step.  Every
-    // instance runs the same iteration sequence whenever it starts, so the results do not depend on capacity;
-    // what changes is that the latency-bound tail of one group overlaps the bulk of the next.
-    const int capacity = cap_slots;
-    const int min_admit = std::max(1, capacity / 32);
-    int next_admit = capacity;
-    bool init_step = true;  // this step runs the INIT pass (step 0, and the step after an admission)
-    // grid bound of the restoration kernels (they read the exact list count on the device): every active instance
-    // until a synchronisation shows how many are restoring (an instance enters at most one step before)
-    // NLOT_RESTO_BOUND=n (test knob, tests/test_resto_gpu.py::test_resto_grid_bound_same_results): the bound forced to
-    // at most n, so that the restoration lists outgrow their grids and the kernels' stride over the exact count runs on
-    // every restoring step (the results must not change)
-    int resto_force = 0;
-    if (const char* e = getenv("NLOT_RESTO_BOUND")) resto_force = std::max(1, atoi(e));
-    int resto_bound = o.resto ? (resto_force ? std::min(Bi, resto_force) : Bi) : 0;
-    int rc = NLOT_OK, n_active = capacity, cur = 0, synced = 0;
-    int64_t step = 0;
-    NLOT_HIP_CHECK(hipMemsetAsync(ws.cnt, 0, 64 * sizeof(int), st));  // both sets, the free-slot count, error flag
-    res.hcnt[0] = capacity;  // step 0's active count (cnt[2] of counter set 0)
-    NLOT_HIP_CHECK(hipMemcpyAsync(ws.cnt + 2, res.hcnt, sizeof(int), hipMemcpyHostToDevice, st));
-    NLOT_HIP_CHECK(hipStreamSynchronize(st));  // the pinned source is reused below
-    // the step's counter bookkeeping as one kernel (k_step_end) writing the pinned ring, or (NLOT_STEP_KERNEL=0) as
-    // the D2H / fill / D2D copies it replaces
-    bool step_kernel = true;
-    if (const char* e = getenv("NLOT_STEP_KERNEL")) step_kernel = atoi(e) != 0;
-    int* dcnt = nullptr;
-    NLOT_HIP_CHECK(hipHostGetDevicePointer((void**)&dcnt, res.hcnt, 0));
-    // fold the counters of steps synced .. last into g_stats (after a synchronisation); updates n_active
-    // NLOT_STEP_LOG=path (diagnostics, scripts/step_trace.py): one line per global step appended to path —
-    // step, active, full-eval instances, trial slots, reused points, Newton solves, restoration count, corrections,
-    // restoration solves, next active
-    const char* step_log = getenv("NLOT_STEP_LOG");
-    std::vector<int> slog;
-    auto fold = [&](int64_t last) {
-        for (int64_t sj = synced; sj <= last; ++sj) {
-            const int j = (int)(sj % kpipe), qj = (int)(sj & 1);
-            const int* hc = res.hcnt + 2 * CSET * j + CSET * qj;
-            const int next_active = res.hcnt[2 * CSET * j + CSET * (qj ^ 1) + 2];
-            if (step_log) {
-                slog.push_back((int)sj);
-                slog.push_back(n_active);
-                for (int c = 0; c < 8; ++c) slog.push_back(c == 2 ? 0 : hc[c]);
-                slog.push_back(next_active);
-                for (int c = 8; c < 11; ++c) slog.push_back(hc[c]);
-            slog.push_back(hc[15]);
-            }
-            g_stats.iterations = (int)(sj + 1);
-            if (use_mlp) {
-                g_stats.mlp_points_full += (int64_t)hc[0] * P;
-                g_stats.mlp_points_value += (int64_t)hc[1] * P;
-                g_stats.mlp_points_full_reused += (int64_t)hc[3];
-                g_stats.mlp_full_launches++;
-                g_stats.mlp_value_launches++;
-            }
-            g_stats.ric_launches++;
-            g_stats.ric_solves += hc[4];
-            g_stats.ric_soc_solves += hc[6];
-            g_stats.ric_resto_solves += hc[7];
-            g_stats.filter_peak = std::max(g_stats.filter_peak, hc[11]);
-            g_stats.filter_forgotten += hc[12];
-            hipEvent_t* e = res.ev[j];
-            if (res.timed[j]) {
-                g_stats.timed_steps++;
-                g_stats.timed_ric_solves += hc[4];
-                if (use_mlp) {
-                    g_stats.timed_points_full += (int64_t)hc[0] * P;
-                    g_stats.timed_points_value += (int64_t)hc[1] * P;
-                    g_stats.timed_points_full_reused += (int64_t)hc[3];
-                }
-            }
-            if (res.timed[j] && use_mlp) {
-                float a = 0, c = 0;
-                (void)hipEventElapsedTime(&a, e[0], e[1]);
-                (void)hipEventElapsedTime(&c, e[2], e[3]);
-                g_stats.mlp_full_ms += a;
-                g_stats.mlp_value_ms += c;
-                if (early_value) {
-                    float v0 = 0;
-                    (void)hipEventElapsedTime(&v0, e[8], e[9]);
-                    g_stats.mlp_value_ms += v0;
-                }
-            }
-            if (res.timed[j]) {
-                float a = 0, r = 0;
-                (void)hipEventElapsedTime(&a, e[4], e[5]);
-                (void)hipEventElapsedTime(&r, e[6], e[7]);
-                g_stats.iterate_ms += a;
-                g_stats.ric_ms += r;
-            }
-            n_active = next_active;
-            if (n_active == 0) break;  // the later steps of this window found nothing to do
-        }
-        synced = last + 1;
-    };
-    // the factorising Newton solves (main stream): the lane-group k_ric
-    auto launch_ric = [&](const int* list, const int* count, int mode, int* diag, int tries) {
-        hipLaunchKernelGGL((k_ric<DYN, false>), dim3((n_active + ric_blocks_per - 1) / ric_blocks_per), dim3(64), 0,
-                           st, dP, dD, dW, list, n_active, count, mode, diag, tries);
-    };
-    for (step = 0; step < max_steps && n_active > 0; ++step) {
-        const int* act = ws.act[cur];
-        int* nxt = ws.act[cur ^ 1];
-        const int* actr = ws.actr[cur];
-        int* nxtr = ws.actr[cur ^ 1];
-        const int kq = step % kpipe;
-        // one step in t_every, at a position in its group of t_every steps that rotates from group to group: the
-        // host's synchronisations (and so admissions, INIT steps) fall at a fixed position of the KPIPE window, so a
-        // fixed sampling phase would time one kind of step only
-        res.timed[kq] = t_every > 0 && step % t_every == (step / t_every) % t_every;
-        hipEvent_t* ev = res.timed[kq] ? res.ev[kq] : res.noev;
-        // Point lists are appended to by the kernel that moves an instance into the phase needing them
-        // (k_iter_b: first line-search round; k_accept: the new iterate, or the next round), so the lists
-        // and counters of step s + 1 fill while step s runs: both alternate by step parity q.
-        const int q = step & 1;
-        int* C = ws.cnt + CSET * q;
-        int* Cn = ws.cnt + CSET * (q ^ 1);
-        if (!step_kernel) NLOT_HIP_CHECK(hipMemsetAsync(Cn, 0, CSET * sizeof(int), st));
-        // the second-order corrections' chain (k_iter_a's SOC pass: their stages; k_ric<DYN, false, true>: the
-        // substitutions) needs no MLP evaluation: it forks to the side stream at the start of the step (soc_fork 1),
-        // after the full MLP launch (2), or after the one k_iter_a launch that also does the evaluations (0)
-        auto soc_chain = [&](bool with_pass) {
-            NLOT_HIP_CHECK(hipEventRecord(res.e_s, st));
-            NLOT_HIP_CHECK(hipStreamWaitEvent(s2, res.e_s, 0));
-            if (with_pass)
-                hipLaunchKernelGGL(k_iter_a<DYN>, dim3(n_active), dim3(64), 0, s2, dP, dD, o, dW, act, ws.x0s, ws.xgs,
-                                   (int)PASS_SOC, C, Cn);
-            hipLaunchKernelGGL((k_ric<DYN, false, true>), dim3((n_active + ric_blocks_per - 1) / ric_blocks_per),
-                               dim3(64), 0, s2, dP, dD, dW, ws.socl, n_active, C + 6, (int)MODE_NEWTON, nullptr, 1 << 30);
-            NLOT_HIP_CHECK(hipEventRecord(res.e_soc, s2));
-            return NLOT_OK;
-        };
-        if (soc_fork == 1) NLOT_HIP_CHECK((hipError_t)(soc_chain(true) == NLOT_OK ? hipSuccess : hipErrorUnknown));
-        // the value launch's first part: the candidates the previous step's k_accept / k_resto_ls listed (ranks
-        // [0, C[14]), C[14] = C[1] now) evaluate on a side stream while this step's evaluations and Newton solves run;
-        // the second part (after k_iter_b) covers the candidates added since (ranks [C[14], C[1]))
-        if (use_mlp && early_value) {
-            if (!step_kernel) NLOT_HIP_CHECK(hipMemcpyAsync(C + 14, C + 1, sizeof(int), hipMemcpyDeviceToDevice, st));
-            NLOT_HIP_CHECK(hipEventRecord(res.e_v0, st));
-            NLOT_HIP_CHECK(hipStreamWaitEvent(s4, res.e_v0, 0));
-            if (ev[0]) (void)hipEventRecord(ev[8], s4);
-            rc = launch_mlp_strided(mlp->dev, ws.tpts[q], (int64_t)n_active * NSPEC, C + 14, (int)P, 0, nullptr,
-                                    mo_t[q], false, s4);
-            if (ev[0]) (void)hipEventRecord(ev[9], s4);
-            if (rc) break;
-            NLOT_HIP_CHECK(hipEventRecord(res.e_v1, s4));
-        }
-        // speculative backtracking only while the GPU is latency-bound (few active instances); in the
-        // throughput-bound bulk it would multiply the value-MLP work for the same accepted steps
-        const int nspec = n_active > spec_threshold ? spec_bulk : NSPEC;
-        if (use_mlp) {
-            if (init_step) hipLaunchKernelGGL(k_points, dim3(n_active), dim3(64), 0, st, dP, dD, dW, act, C);
-            if (ev[0]) (void)hipEventRecord(ev[0], st);
-            // contiguous rank-major list: P_per = 1, count = (#instances) * P read on the device
-            MlpReuse ru = reuse[q ^ 1];  // the previous step's trial list
-            ru.nreused = C + 3;          // statistics: points whose forward was reused
-            rc = launch_mlp_strided(mlp->dev, ws.pts, n_active, C + 0, (int)P, 0, nullptr, mo, true, st, &ru);
-            if (rc) break;
-            if (ev[0]) (void)hipEventRecord(ev[1], st);
-        }
-        if (soc_fork == 2) NLOT_HIP_CHECK((hipError_t)(soc_chain(true) == NLOT_OK ? hipSuccess : hipErrorUnknown));
-        if (ev[4]) (void)hipEventRecord(ev[4], st);
-        // restoration phases (list actr, count C[5]) on a stream of their own, forked once the step's evaluations are
-        // in (they need nothing else of the step; disjoint instances): k_resto_a, their Newton solves, k_resto_b.  An
-        // instance k_resto_a returns to the original problem is passed by this step's k_iter_a and continues next
-        // step (k_accept); round 5: k_resto_a (one long wavefront per restoring instance, ~0.5 ms) left the main
-        // stream's critical path
-        const int n_resto = std::min(n_active, resto_bound);
-        if (n_resto > 0) {
-            NLOT_HIP_CHECK(hipEventRecord(res.e_a, st));
-            NLOT_HIP_CHECK(hipStreamWaitEvent(s3, res.e_a, 0));
-            hipLaunchKernelGGL(k_resto_a<DYN>, dim3(n_resto), dim3(64), 0, s3, dP, dD, o, dW, actr, ws.x0s, ws.xgs, C);
-            hipLaunchKernelGGL((k_ric<DYN, true>), dim3((n_resto + ric_blocks_per - 1) / ric_blocks_per), dim3(64), 0, s3,
-                               dP, dD, dW, actr, n_resto, C + 5, (int)MODE_NEWTON, C + 15,
-                               resto_tries && n_active > ric_tries_min ? ric_tries : 1 << 30);
-            hipLaunchKernelGGL(k_resto_b<DYN>, dim3(n_resto), dim3(64), 0, s3, dP, dD, o, dW, actr, C,
-                               use_mlp ? ws.tpts[q] : nullptr);
-            NLOT_HIP_CHECK(hipEventRecord(res.e_r, s3));
-        }
-        if (init_step) {  // INIT: slack push + least-squares multipliers (one Riccati solve)
-            hipLaunchKernelGGL(k_iter_a<DYN>, dim3(n_active), dim3(64), 0, st, dP, dD, o, dW, act, ws.x0s, ws.xgs,
-                               (int)PASS_INIT, C, Cn);
-            launch_ric(act, C + 2, (int)MODE_LSQ, nullptr, 1 << 30);
-        }
-        hipLaunchKernelGGL(k_iter_a<DYN>, dim3(n_active), dim3(64), 0, st, dP, dD, o, dW, act, ws.x0s, ws.xgs,
-                           (int)(soc_fork == 0 ? PASS_ALL : PASS_EVAL), C, Cn);
-        if (soc_fork == 0) NLOT_HIP_CHECK((hipError_t)(soc_chain(false) == NLOT_OK ? hipSuccess : hipErrorUnknown));
-        // the Newton solves and the corrections run over the compacted lists k_iter_a wrote (ws.ricl / ws.socl,
-        // counts C[4] / C[6]; the grids are host bounds, blocks past the count exit): one group per instance that
-        // has work, so a launch holds as many wavefronts as it has solves / 4
-        if (ev[6]) (void)hipEventRecord(ev[6], st);
-        launch_ric(ws.ricl, C + 4, (int)MODE_NEWTON, C + 8, n_active > ric_tries_min ? ric_tries : 1 << 30);
-        if (ev[6]) (void)hipEventRecord(ev[7], st);
-        NLOT_HIP_CHECK(hipStreamWaitEvent(st, res.e_soc, 0));
-        hipLaunchKernelGGL(k_iter_b<DYN>, dim3(n_active), dim3(64), 0, st, dP, dD, o, dW, act, C,
-                           use_mlp ? ws.tpts[q] : nullptr, Cn);
-        if (n_resto > 0) NLOT_HIP_CHECK(hipStreamWaitEvent(st, res.e_r, 0));
-        if (ev[4]) (void)hipEventRecord(ev[5], st);
-        if (use_mlp) {
-            // the wait for the early part comes before the timing event: ev[2]..ev[3] is the second part's own time
-            if (early_value) NLOT_HIP_CHECK(hipStreamWaitEvent(st, res.e_v1, 0));
-            if (ev[0]) (void)hipEventRecord(ev[2], st);
-            MlpReuse vb{};
-            vb.base = C + 14;
-            rc = launch_mlp_strided(mlp->dev, ws.tpts[q], (int64_t)n_active * NSPEC, C + 1, (int)P, 0, nullptr,
-                                    mo_t[q], false, st, early_value ? &vb : nullptr);
-            if (rc) break;
-            if (ev[0]) (void)hipEventRecord(ev[3], st);
-        }
-        // the next round's candidate count uses this step's nspec (n_active only shrinks: speculation
-        // starts at most KPIPE steps late; the accepted alpha is the same either way)
-        if (n_resto > 0)
-            hipLaunchKernelGGL(k_resto_ls<DYN>, dim3(n_resto), dim3(64), 0, st, dP, dD, o, dW, actr, ws.x0s, ws.xgs, C, Cn,
-                               use_mlp ? ws.tpts[q ^ 1] : nullptr, use_mlp ? ws.tval[q] : nullptr, nspec);
-        hipLaunchKernelGGL(k_accept<DYN>, dim3(n_active), dim3(64), 0, st, dP, dD, o, dW, act, nxt, nxtr, ws.x0s, ws.xgs, C, Cn,
-                           use_mlp ? ws.tpts[q ^ 1] : nullptr, use_mlp ? ws.tval[q] : nullptr, nspec);
-        NLOT_HIP_CHECK(hipGetLastError());
-        // this step's counters (C) and the next step's active count (Cn[2]), before step + 1 clears C
-        int* hflag = res.hcnt + KPIPE * 2 * CSET;
-        if (step_kernel) {
-            hipLaunchKernelGGL(k_step_end, dim3(1), dim3(64), 0, st, ws.cnt, q, dcnt + 2 * CSET * kq,
-                               dcnt + KPIPE * 2 * CSET);
-        } else {
-            NLOT_HIP_CHECK(hipMemcpyAsync(res.hcnt + 2 * CSET * kq, ws.cnt, 2 * CSET * sizeof(int),
-                                          hipMemcpyDeviceToHost, st));
-        }
-        cur ^= 1;
-        init_step = false;
-        if (kq != kpipe - 1) continue;
-        if (!step_kernel)
-            NLOT_HIP_CHECK(hipMemcpyAsync(hflag, ws.cnt + 2 * CSET, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-        NLOT_HIP_CHECK(hipStreamSynchronize(st));
-        if (hflag[1] != 0) {  // k_admit's shortfall or a list that outgrew its grid (grid_guard): fail now, not at the end
-            set_error(grid_error(hflag[1]));
-            return NLOT_ERR_INVALID;
-        }
-        // restoration lists of the window: the next launches' grid bound (their kernels read the exact count)
-        int rmax = 0;
-        for (int j = 0; j <= kq; ++j) rmax = std::max(rmax, res.hcnt[2 * CSET * j + CSET * (((step - kq + j) & 1) ^ 1) + 5]);
-        resto_bound = std::min(Bi, 2 * rmax + 256);
-        if (resto_force) resto_bound = std::min(resto_bound, resto_force);
-        fold(step);
-        if (progress_s > 0) {  // NLOT_PROGRESS=seconds: a line on stderr now and then (long continuous calls)
-            const double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_prog0).count();
-            if (t >= t_prog) {
-                fprintf(stderr, "[nlot] %.0f s: step %lld, %d active, %d of %d instances admitted\n", t, (long long)step,
-                        n_active, next_admit, Bi);
-                fflush(stderr);
-                t_prog = t + progress_s;
-            }
-        }
-        if (next_admit < Bi && (capacity - n_active >= min_admit || n_active == 0)) {
-            // instances next_admit .. next_admit + n_new - 1 take free slots (the free-slot count is capacity - the
-            // next active count: every instance that left the list freed its slot), join the next step's active
-            // list, and start (k_init_state on those slots)
-            const int n_new = std::min(capacity - n_active, Bi - next_admit);
-            int* Cadm = ws.cnt + CSET * ((step + 1) & 1);
-            hipLaunchKernelGGL(k_admit, dim3(1), dim3(1024), 0, st, ws.act[cur], Cadm, ws.sinst, ws.freel,
-                               ws.cnt + 2 * CSET, next_admit, n_new);
-            hipLaunchKernelGGL(k_init_state, dim3(n_new), dim3(64), 0, st, dP, dD, o, ws, x0, xg, Xinit, ws.act[cur],
-                               Cadm);
-            NLOT_HIP_CHECK(hipGetLastError());
-            next_admit += n_new;
-            n_active += n_new;
-            init_step = true;
-        }
-    }
-    if (rc) return rc;
-    if (synced < step) {  // a window the loop left before its synchronisation point
-        NLOT_HIP_CHECK(hipStreamSynchronize(st));
-        fold(step - 1);
-    }
-#ifdef NLOT_KPROF
-    {
-        unsigned long long kp[4][16];
-        NLOT_HIP_CHECK(hipStreamSynchronize(st));
-        NLOT_HIP_CHECK(hipMemcpyFromSymbol(kp, HIP_SYMBOL(g_kprof), sizeof(kp)));
-        const char* kn[4] = {"k_iter_a", "k_iter_b", "k_accept", "k_resto"};
-        for (int k = 0; k < 4; ++k)
-            if (kp[k][15]) {
-                fprintf(stderr, "[kprof] %s waves %llu: us per wave", kn[k], kp[k][15]);
-                for (int i = 0; i < 15; ++i)
-                    if (kp[k][i]) fprintf(stderr, " [%d] %.2f", i, kp[k][i] * 1e-2 / kp[k][15]);
-                fprintf(stderr, "\n");
-            }
-        const unsigned long long z[4][16] = {};
-        NLOT_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_kprof), z, sizeof(z)));
-    }
-#endif
-#ifdef NLOT_RIC_PROF
-    {
-        unsigned long long hp[3][5];
-        NLOT_HIP_CHECK(hipStreamSynchronize(st));
-        NLOT_HIP_CHECK(hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_ric_prof), sizeof(hp)));
-        const char* kinds[3] = {"newton", "correction", "restoration"};
-        for (int k = 0; k < 3; ++k)
-            if (hp[k][4])
-                fprintf(stderr, "[ric_prof] %s solves %llu: us per solve backward %.2f F1 %.2f F2 %.2f F3+mult %.2f\n",
-                        kinds[k], hp[k][4], hp[k][0] * 1e-2 / hp[k][4], hp[k][1] * 1e-2 / hp[k][4],
-                        hp[k][2] * 1e-2 / hp[k][4], hp[k][3] * 1e-2 / hp[k][4]);
-        const unsigned long long z[3][5] = {};
-        NLOT_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_ric_prof), z, sizeof(z)));
-    }
-#endif
-    if (n_active > 0 || next_admit < Bi) {
-        set_error("nlot_solve_batch: the global step cap was reached with instances unfinished (phase-machine bug)");
-        return NLOT_ERR_INVALID;
-    }
-    if (step_log && !slog.empty()) {
-        if (FILE* f = fopen(step_log, "a")) {
-            for (size_t i = 0; i < slog.size(); i += 15) {
-                for (int c = 0; c < 15; ++c) fprintf(f, c ? " %d" : "%d", slog[i + c]);
-                fputc('\n', f);
-            }
-            fclose(f);
-        }
-    }
-    // every instance wrote its outputs when it left the active list (k_accept -> retire)
-    NLOT_HIP_CHECK(hipMemcpyAsync(res.hcnt, ws.cnt + 2 * CSET, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    NLOT_HIP_CHECK(hipStreamSynchronize(st));
-    if (res.hcnt[1] != 0 || res.hcnt[0] != capacity) {
-        set_error(res.hcnt[1] != 0 ? grid_error(res.hcnt[1])
-                                   : "nlot_solve_batch: slot bookkeeping mismatch (free slots at the end != capacity)");
-        return NLOT_ERR_INVALID;
-    }
-    return NLOT_OK;
-}
+// ---------------------------------------------------------------------------------------------
+// host driver: run<DYN>() (nlot_solver_run.h), instantiated per compile unit (Makefile): NLOT_UNIT = D instantiates
+// run<D> (Euler) and run<D + NLOT_RK4_BIAS> (RK4); a kernel-tuning build (make tune) run<NLOT_ONLY_DYN> alone.
+// The C ABI, the statistics and the dispatch are in nlot_solve_api.hip.
+// ---------------------------------------------------------------------------------------------
+#include "nlot_solver_run.h"
+
+namespace nlot {
 
 #define NLOT_RUN_SIG(D)                                                                                            \
     int run<D>(const NlotProblem&, const NlotSolverOptions&, const NlotMlp*, const double*, const double*,          \
                const double*, double*, double*, double*, double*, int32_t*, int32_t*, int64_t, void*, hipStream_t)
-#if defined(NLOT_UNIT) && NLOT_UNIT >= 0
+#if defined(NLOT_ONLY_DYN)
+template NLOT_RUN_SIG(NLOT_ONLY_DYN);
+#elif defined(NLOT_UNIT)
 template NLOT_RUN_SIG(NLOT_UNIT);
 template NLOT_RUN_SIG(NLOT_UNIT + NLOT_RK4_BIAS);
-#elif defined(NLOT_UNIT)
-#define NLOT_EXTERN_RUN(D) extern template NLOT_RUN_SIG(D); extern template NLOT_RUN_SIG(D + NLOT_RK4_BIAS);
-NLOT_EXTERN_RUN(0) NLOT_EXTERN_RUN(1) NLOT_EXTERN_RUN(2) NLOT_EXTERN_RUN(3) NLOT_EXTERN_RUN(4) NLOT_EXTERN_RUN(5)
-#undef NLOT_EXTERN_RUN
+#else
+#error "nlot_solver.hip: compile with -DNLOT_UNIT=<dynamics model 0..5> (or -DNLOT_ONLY_DYN=<instantiation>)"
 #endif
 #undef NLOT_RUN_SIG
 
 }  // namespace nlot
-
-#if !defined(NLOT_UNIT) || NLOT_UNIT < 0
-extern "C" size_t nlot_solve_workspace_size(const NlotProblem* p, int64_t B) {
-    if (!p) return 0;
-    nlot::Dims d = nlot::make_dims(*p);
-    return nlot::ws_bytes(d, B, p->sdf_kind == NLOT_SDF_MLP);
-}
-extern "C" size_t nlot_solve_workspace_size_slots(const NlotProblem* p, int64_t B, int32_t max_active) {
-    return nlot_solve_workspace_size(p, max_active > 0 && max_active < B ? (int64_t)max_active : B);
-}
-
-extern "C" int32_t nlot_solve_batch(const NlotProblem* p, const NlotSolverOptions* o, const NlotMlp* mlp,
-                                    const double* x0, const double* xg, const double* Xinit, double* X, double* U,
-                                    double* S, double* cost, int32_t* status, int32_t* iters, int64_t B,
-                                    void* workspace, size_t wbytes, void* stream) {
-    using namespace nlot;
-    int rc = validate(p, o, mlp, B);
-    if (rc) return rc;
-    if (!x0 || !xg || !X || !U || !cost || !status || !iters || !workspace) {
-        set_error("nlot_solve_batch: null pointer");
-        return NLOT_ERR_INVALID;
-    }
-    if (wbytes < nlot_solve_workspace_size_slots(p, B, o->max_active)) {
-        set_error("nlot_solve_batch: workspace too small");
-        return NLOT_ERR_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    // the dynamics model and the integrator select the instantiation (Euler: DYN; RK4: DYN + NLOT_RK4_BIAS)
-#ifdef NLOT_ONLY_DYN  // kernel-tuning builds (make tune): the one instantiation
-    if (p->dynamics + (p->integrator == NLOT_INTEG_RK4 ? NLOT_RK4_BIAS : 0) == NLOT_ONLY_DYN)
-        return run<NLOT_ONLY_DYN>(*p, *o, mlp, x0, xg, Xinit, X, U, S, cost, status, iters, B, workspace, st);
-    set_error("tuning build (NLOT_ONLY_DYN): this dynamics model is not compiled in");
-    return NLOT_ERR_INVALID;
-#endif
-#define NLOT_RUN(D) return run<D>(*p, *o, mlp, x0, xg, Xinit, X, U, S, cost, status, iters, B, workspace, st)
-#ifndef NLOT_ONLY_DYN
-    switch (p->dynamics + (p->integrator == NLOT_INTEG_RK4 ? NLOT_RK4_BIAS : 0)) {
-    case NLOT_POINT_1ST: NLOT_RUN(NLOT_POINT_1ST);
-    case NLOT_POINT_2ND: NLOT_RUN(NLOT_POINT_2ND);
-    case NLOT_UNICYCLE: NLOT_RUN(NLOT_UNICYCLE);
-    case NLOT_UNICYCLE_2ND: NLOT_RUN(NLOT_UNICYCLE_2ND);
-    case NLOT_ACKERMANN: NLOT_RUN(NLOT_ACKERMANN);
-    case NLOT_ACKERMANN_2ND: NLOT_RUN(NLOT_ACKERMANN_2ND);
-    case NLOT_POINT_1ST + NLOT_RK4_BIAS: NLOT_RUN(NLOT_POINT_1ST + NLOT_RK4_BIAS);
-    case NLOT_POINT_2ND + NLOT_RK4_BIAS: NLOT_RUN(NLOT_POINT_2ND + NLOT_RK4_BIAS);
-    case NLOT_UNICYCLE + NLOT_RK4_BIAS: NLOT_RUN(NLOT_UNICYCLE + NLOT_RK4_BIAS);
-    case NLOT_UNICYCLE_2ND + NLOT_RK4_BIAS: NLOT_RUN(NLOT_UNICYCLE_2ND + NLOT_RK4_BIAS);
-    case NLOT_ACKERMANN + NLOT_RK4_BIAS: NLOT_RUN(NLOT_ACKERMANN + NLOT_RK4_BIAS);
-    case NLOT_ACKERMANN_2ND + NLOT_RK4_BIAS: NLOT_RUN(NLOT_ACKERMANN_2ND + NLOT_RK4_BIAS);
-    }
-#endif
-#undef NLOT_RUN
-    set_error("unknown dynamics");
-    return NLOT_ERR_INVALID;
-}
-
-extern "C" void nlot_set_timing(int32_t every) { nlot::g_timing = every > 0 ? every : 0; }
-extern "C" void nlot_last_stats(NlotSolveStats* out) {
-    if (out) *out = nlot::g_stats;
-}
-#endif  // C ABI unit

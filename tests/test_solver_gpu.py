@@ -279,6 +279,10 @@ def test_continuous_batching_same_results(artefact, case):
     {"NLOT_EARLY_VALUE": "0"},                               # no early value launch (default on since round 4)
     {"NLOT_SPEC_THRESHOLD": "100000", "NLOT_SPEC_BULK": "4"},
     {"NLOT_STEP_KERNEL": "0"},                               # counter copies as D2H / fill / D2D instead of k_step_end
+    {"NLOT_PIPE": "1"},                                      # the host synchronises after every step
+    {"NLOT_MLP_REUSE": "0"},                                 # the full MLP launch recomputes every forward
+    {"NLOT_STREAM_PRIO": "2"},                               # restoration and correction streams at the highest priority
+    {"NLOT_RIC_TRIES": "3"},                                 # up to three delta_w attempts per k_ric launch
 ])
 def test_scheduling_knobs_same_results(artefact, knobs, monkeypatch):
     """The solver's scheduling (attempt cap per launch, stream layout, speculation) changes when an instance's work
