@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 17
+#define NLOT_ABI_VERSION 18
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -426,6 +426,54 @@ void nlot_default_rollout_options(NlotRolloutOptions* opt);
 int32_t nlot_rollout_batch(const NlotProblem* prob, const NlotRolloutOptions* opt, const double* X, const double* U,
                            const double* xg, double* X_roll, double* clearance, int32_t* where, double* deviation,
                            int32_t* dev_where, double* goal_error, int32_t* flags, int64_t B, void* stream);
+
+/* ---- the analytic scene at arbitrary points, and SDF-quality metrics (ABI v18) ------------------
+ * nlot_scene_sdf_eval evaluates the scene the solver (approximated), the RRT, nlot_verify_batch and nlot_rollout_batch
+ * (exact) see, at caller-given points; nlot_sdf_metrics is the reference's compute_metrics (run_benchmark.py:34-46,
+ * core/metrics.py) on two sampled SDFs.  Both are asynchronous on `stream`, take no workspace
+ * and keep no global state: the problem and every temporary live in stream-ordered allocations. */
+#define NLOT_SCENE_EXACT 0   /* MultiObstacle.sdf casadi.py:381-383: the min of the obstacles' exact SDFs */
+#define NLOT_SCENE_APPROX 1  /* MultiObstacle.approximated_sdf casadi.py:385-386 (soft_min, prob->softmin_alpha): the
+                                function the analytic-mode solver constrains */
+/* val[i] = the scene's SDF of kind `kind` at pts[i], the scene being prob->obs whatever prob->sdf_kind says (like
+ * nlot_verify_batch); only the scene fields of `prob` (n_obs, n_verts, obs, verts, softmin_alpha) are read.
+ *   pts [P][2], val [P] fp64 device; grad [P][2] (d/dx, d/dy) and hess [P][3] (xx, xy, yy) fp64 device or NULL, each on
+ *   its own, for NLOT_SCENE_APPROX only (the exact SDF has no derivative code).
+ * A point's outputs depend on that point and the scene only: they are bitwise the same wherever the point sits in
+ * `pts` and whatever P is.
+ * NLOT_ERR_INVALID before any device call for: a null prob, pts or val; kind outside {0, 1}; n_obs == 0; an invalid
+ * scene (n_obs, n_verts, an obstacle type or a vertex range out of bounds); P outside 1 .. 2^30; grad or hess with
+ * NLOT_SCENE_EXACT. */
+int32_t nlot_scene_sdf_eval(const NlotProblem* prob, int32_t kind, const double* pts, int64_t P, double* val,
+                            double* grad, double* hess, void* stream);
+
+typedef struct NlotSdfMetricsOptions {
+    double threshold; /* the occupied sets are sdf < threshold (0) */
+    double eps;       /* the surface bands are |sdf| < eps (1e-2) */
+} NlotSdfMetricsOptions;
+typedef struct NlotSdfMetrics { /* 64 bytes, written on the device */
+    double mse;          /* mean of (target - pred)^2 */
+    double iou;          /* |{target < threshold} and {pred < threshold}| / |... or ...|; 1.0 when the union is empty */
+    double hausdorff;    /* max(max_{q in Q} min_{t in T} |q - t|, max_{t in T} min_{q in Q} |t - q|), T = {pts[i] :
+                            |target[i]| < eps}, Q = {pts[i] : |pred[i]| < eps}; NaN when T or Q is empty */
+    double chamfer;      /* (mean_{q in Q} min_t |q - t| + mean_{t in T} min_q |t - q|) / 2; NaN when T or Q is empty */
+    double surface_loss; /* mean of pred[i]^2 over i in T; NaN when T is empty */
+    int64_t n_target_surface, n_pred_surface; /* |T|, |Q| */
+    int64_t n_points;    /* P */
+} NlotSdfMetrics;
+/* Fill `opt` with the defaults documented above. */
+void nlot_default_sdf_metrics_options(NlotSdfMetricsOptions* opt);
+/* The metrics of core/metrics.py of `pred` against `target`, two SDFs sampled at the same P points.
+ *   pts [P][2], target [P], pred [P] fp64 device; out: one NlotSdfMetrics in device memory.
+ * Comparisons are IEEE: a NaN entry of target or pred is in no set and makes mse NaN; it is not flagged otherwise.
+ * The nearest-neighbour distances are brute force over T x Q in fp64 (min of squared distances, one sqrt).
+ * The same inputs give bitwise the same NlotSdfMetrics on every call (index-ordered compaction, fixed-order
+ * reductions, no floating-point atomics).  The stream-ordered temporaries are 32 P bytes for the two bands (their
+ * sizes are not known on the host) plus 176 bytes per 1024 points of per-block records.
+ * NLOT_ERR_INVALID before any device call for: a null pointer; P outside 1 .. 2^30; eps not > 0 or not finite; a
+ * non-finite threshold. */
+int32_t nlot_sdf_metrics(const NlotSdfMetricsOptions* opt, const double* pts, const double* target, const double* pred,
+                         int64_t P, NlotSdfMetrics* out, void* stream);
 casadi_int_t nn_sdf_n_in(void);
 casadi_int_t nn_sdf_n_out(void);
 const casadi_int_t* nn_sdf_sparsity_in(casadi_int_t i);

@@ -153,3 +153,24 @@ def rollout_options(substeps=8, edge_points=3, clearance_min=0.0, deviation_tol=
     """The defaults of nlot_default_rollout_options (the deviation and goal thresholds are off)."""
     return NlotRolloutOptions(substeps=int(substeps), edge_points=int(edge_points), clearance_min=float(clearance_min),
                               deviation_tol=float(deviation_tol), goal_tol=float(goal_tol))
+
+
+# nlot_scene_sdf_eval / nlot_sdf_metrics (include/nlot.h, ABI v18)
+SCENE_EXACT, SCENE_APPROX = 0, 1
+
+
+class NlotSdfMetricsOptions(C.Structure):
+    """include/nlot.h NlotSdfMetricsOptions."""
+    _fields_ = [("threshold", C.c_double), ("eps", C.c_double)]
+
+
+class NlotSdfMetrics(C.Structure):
+    """include/nlot.h NlotSdfMetrics (64 bytes, written on the device)."""
+    _fields_ = [("mse", C.c_double), ("iou", C.c_double), ("hausdorff", C.c_double), ("chamfer", C.c_double),
+                ("surface_loss", C.c_double), ("n_target_surface", C.c_int64), ("n_pred_surface", C.c_int64),
+                ("n_points", C.c_int64)]
+
+
+def sdf_metrics_options(threshold=0.0, eps=1e-2) -> NlotSdfMetricsOptions:
+    """The defaults of nlot_default_sdf_metrics_options (core/metrics.py's threshold and eps)."""
+    return NlotSdfMetricsOptions(threshold=float(threshold), eps=float(eps))

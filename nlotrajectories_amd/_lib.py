@@ -25,6 +25,7 @@ EXPORTED = [
     "adj1_nn_sdf_n_in", "adj1_nn_sdf_n_out", "adj1_nn_sdf", "jac_adj1_nn_sdf_n_in",
     "jac_adj1_nn_sdf_n_out", "jac_adj1_nn_sdf", "nlot_rrt_workspace_size", "nlot_rrt_init",
     "nlot_default_verify_options", "nlot_verify_batch", "nlot_default_rollout_options", "nlot_rollout_batch",
+    "nlot_scene_sdf_eval", "nlot_default_sdf_metrics_options", "nlot_sdf_metrics",
 ]
 
 
@@ -88,9 +89,15 @@ def lib():
     L.nlot_rollout_batch.argtypes = [C.POINTER(_abi.NlotProblem), C.POINTER(_abi.NlotRolloutOptions), vp, vp, vp, vp, vp,
                                      vp, vp, vp, vp, vp, C.c_int64, vp]
     L.nlot_rollout_batch.restype = C.c_int32
+    L.nlot_scene_sdf_eval.argtypes = [C.POINTER(_abi.NlotProblem), C.c_int32, vp, C.c_int64, vp, vp, vp, vp]
+    L.nlot_scene_sdf_eval.restype = C.c_int32
+    L.nlot_default_sdf_metrics_options.argtypes = [C.POINTER(_abi.NlotSdfMetricsOptions)]
+    L.nlot_default_sdf_metrics_options.restype = None
+    L.nlot_sdf_metrics.argtypes = [C.POINTER(_abi.NlotSdfMetricsOptions), vp, vp, vp, C.c_int64, vp, vp]
+    L.nlot_sdf_metrics.restype = C.c_int32
     L.nlot_casadi_bind.argtypes = [vp]
     L.nlot_casadi_bind.restype = C.c_int32
-    if L.nlot_abi_version() != 17:
+    if L.nlot_abi_version() != 18:
         raise NlotError("libnlot.so ABI version mismatch")
     _lib = L
     return L

@@ -17,7 +17,10 @@ Differences from the reference, all loud:
   * --verify (off by default) measures the returned trajectory against the scene's exact SDF between the knots
     and along the footprint's edges (verify.py) and prints three more lines; nothing else changes;
   * --rollout (off by default) rolls the returned controls forward through the continuous dynamics (rollout.py:
-    sub-stepped RK4, zero-order hold, open loop) and prints four more lines, after --verify's; nothing else changes.
+    sub-stepped RK4, zero-order hold, open loop) and prints four more lines, after --verify's; nothing else changes;
+  * --metrics-device gpu (default host) computes the SDF-quality metrics on the device (scene_gpu.scene_metrics: the
+    solver's own scene functions and a brute-force nearest-neighbour kernel) instead of scene.py's numpy; the CSV is
+    the same to rounding.  --train-sdf-device gpu does the same for the training targets of `--weights train`.
 """
 from __future__ import annotations
 
@@ -40,9 +43,19 @@ CSV_HEADER = ("solver_mode,model_type,num_hidden_layers,hidden_dim,activation_fu
               "hausdorff,chamfer,surface_loss,enforce_heading,use_smooth,smooth_weight")
 
 
-def _metrics(cfg: Config, mlp, n=1000, lo=-1.0, hi=2.0):
-    """run_benchmark.py:35-46 compute_metrics: approximated vs exact SDF on an n x n grid of [-1, 2]^2."""
+def _metrics(cfg: Config, mlp, n=1000, lo=-1.0, hi=2.0, device="host"):
+    """run_benchmark.py:35-46 compute_metrics: approximated vs exact SDF on an n x n grid of [-1, 2]^2, in numpy
+    (device="host", scene.py) or on the GPU (device="gpu", scene_gpu.scene_metrics)."""
     obs = cfg.obstacle_dicts()
+    if device == "gpu":
+        from .scene_gpu import scene_metrics
+
+        try:
+            return scene_metrics(obs, mlp, n=n, lo=lo, hi=hi)
+        except NotImplementedError:
+            return (None,) * 5
+    if device != "host":
+        raise ValueError(f"metrics device must be 'host' or 'gpu', not {device!r}")
     x = np.linspace(lo, hi, n)
     X, Y = np.meshgrid(x, x)
     try:
@@ -88,7 +101,7 @@ def _print_rollout(prob, r, xg, substeps, edge_points):
 
 def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="results", verbose=True,
                   options=None, metrics=True, verify=False, verify_sub=8, verify_edge_points=3, rollout=False,
-                  rollout_substeps=8, rollout_edge_points=3):
+                  rollout_substeps=8, rollout_edge_points=3, metrics_device="host", train_sdf_device="host"):
     """Returns (X_opt [nx, N+1], U_opt [nu, N], status str) like RunBenchmark.run (runner.py:148-153).
     verify=True also prints the trajectory's exact clearance, dynamics defect and collision verdict; rollout=True the
     clearance, deviation from the plan and goal error of the controls rolled through the continuous dynamics."""
@@ -106,7 +119,7 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
         if weights == "train":  # run_benchmark.py:84-95
             from .trainer import train_for_config
 
-            model, _ = train_for_config(cfg, verbose=verbose)
+            model, _ = train_for_config(cfg, verbose=verbose, sdf_device=train_sdf_device)
             w = MlpWeights.from_module(model)
         else:
             w = MlpWeights.artefact() if weights == "artefact" else MlpWeights.load(weights)
@@ -149,7 +162,7 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
         return X, U, status
     print("Objective value:", obj)
     print("Computation time for the solver:", solver_time)
-    m = _metrics(cfg, mlp) if metrics else (None,) * 5
+    m = _metrics(cfg, mlp, device=metrics_device) if metrics else (None,) * 5
     for name, v in zip(("MSE", "IoU", "Hausdorff", "Chamfer", "Surface loss"), m):
         print(f"{name}:", v)
     print("Optimization complete.")
@@ -196,7 +209,7 @@ def _f(prob, X, U):
                      (x[6] / (1 + x[3] ** 2) * x[4] + np.tan(x[3]) * u[0]) / L, u[0], u[1]])
 
 
-def main(argv=None):
+def _parser():
     ap = argparse.ArgumentParser(prog="run-benchmark")
     ap.add_argument("--config", type=str, required=True, help="Path to benchmark YAML config")
     ap.add_argument("--initializer", choices=["yaml", "linear", "default", "rrt"], default="yaml",
@@ -213,10 +226,19 @@ def main(argv=None):
                          "open loop) and report the rolled motion's clearance, deviation and goal error (rollout.py)")
     ap.add_argument("--rollout-substeps", type=int, default=8, help="--rollout: RK4 steps per interval")
     ap.add_argument("--rollout-edge-points", type=int, default=3, help="--rollout: interior points per footprint edge")
-    a = ap.parse_args(argv)
+    ap.add_argument("--metrics-device", choices=["host", "gpu"], default="host",
+                    help="where the SDF-quality metrics are computed: numpy (scene.py) or the GPU (scene_gpu.py)")
+    ap.add_argument("--train-sdf-device", choices=["host", "gpu"], default="host",
+                    help="--weights train: where the training targets (the scene's exact SDF) are evaluated")
+    return ap
+
+
+def main(argv=None):
+    a = _parser().parse_args(argv)
     run_benchmark(Path(a.config), initializer=a.initializer, weights=a.weights, results_dir=a.results, verify=a.verify,
                   verify_sub=a.verify_sub, verify_edge_points=a.verify_edge_points, rollout=a.rollout,
-                  rollout_substeps=a.rollout_substeps, rollout_edge_points=a.rollout_edge_points)
+                  rollout_substeps=a.rollout_substeps, rollout_edge_points=a.rollout_edge_points,
+                  metrics_device=a.metrics_device, train_sdf_device=a.train_sdf_device)
 
 
 if __name__ == "__main__":

@@ -83,8 +83,12 @@ class NNObstacleTrainer:
 
     def __init__(self, obstacles, model: nn.Module, device=None, epochs: int = 100, eikonal_weight: float = 0,
                  surface_loss_weight: float = 0, n_samples: int = 200000, boundary_fraction: float = 0.3,
-                 random: bool = True, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, verbose: bool = True):
+                 random: bool = True, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, verbose: bool = True,
+                 sdf_device: str = "host"):
+        if sdf_device not in ("host", "gpu"):
+            raise ValueError(f"sdf_device must be 'host' or 'gpu', not {sdf_device!r}")
         self.obstacles = obstacles
+        self.sdf_device = sdf_device
         if device is None:
             device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.device = torch.device(device)
@@ -100,6 +104,14 @@ class NNObstacleTrainer:
             print(f"Using surface loss weight: {surface_loss_weight}, eikonal weight: {eikonal_weight}", flush=True)
 
     def sdf(self, x, y):
+        """The scene's exact SDF on numpy arrays: scene.py on the host, or (sdf_device="gpu") the device's exact_sdf
+        through scene_gpu.scene_sdf_eval."""
+        if self.sdf_device == "gpu":
+            from .scene_gpu import scene_sdf_eval
+
+            x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+            v = scene_sdf_eval(self.obstacles, np.stack([x.ravel(), y.ravel()], 1), "exact")
+            return v.cpu().numpy().reshape(x.shape)
         return scene.exact_sdf(self.obstacles, x, y)
 
     def generate_data(self, x_range, y_range, n_samples, random=True):
@@ -188,11 +200,12 @@ def model_from_config(mc):
     raise ValueError(f"Unsupported model type: {mc.type}")
 
 
-def train_for_config(cfg, seed=0, device=None, epochs=100, verbose=True):
+def train_for_config(cfg, seed=0, device=None, epochs=100, verbose=True, sdf_device="host"):
     """run_benchmark.py:84-95: train the config's network on its scene over (-0.5, 1.5)^2."""
     mc = cfg.model
     model = model_from_config(mc)
     tr = NNObstacleTrainer(cfg.obstacle_dicts(), model, device=device, epochs=epochs, n_samples=mc.n_samples,
                            boundary_fraction=mc.boundary_fraction, eikonal_weight=mc.eikonal_loss_weight,
-                           surface_loss_weight=mc.surface_loss_weight, seed=seed, verbose=verbose)
+                           surface_loss_weight=mc.surface_loss_weight, seed=seed, verbose=verbose,
+                           sdf_device=sdf_device)
     return tr.train((-0.5, 1.5), (-0.5, 1.5)), tr
