@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 18
+#define NLOT_ABI_VERSION 19
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -474,6 +474,90 @@ void nlot_default_sdf_metrics_options(NlotSdfMetricsOptions* opt);
  * non-finite threshold. */
 int32_t nlot_sdf_metrics(const NlotSdfMetricsOptions* opt, const double* pts, const double* target, const double* pred,
                          int64_t P, NlotSdfMetrics* out, void* stream);
+/* ---- time-varying LQR gains about a plan, and the closed-loop tracking rollout (ABI v19) ---------
+ * nlot_rollout_batch is open loop.  What tracks a plan on a robot is a feedback law about it; these two calls give
+ * the standard one and measure what it does in the scene.
+ *
+ * Phi(x, u) is ONE classical RK4 step of size prob->dt of the problem's continuous dynamics with u held constant,
+ * WHATEVER prob->integrator says: nlot_rollout_batch's flow at substeps = 1.  A_k = dPhi/dx and B_k = dPhi/du, both at
+ * (X_k, U_k), by forward-mode differentiation of that step (exact to rounding).  With Q = diag(q), Qf = diag(qf),
+ * R = diag(r):
+ *   P_N = Qf;  for k = N - 1 .. 0:
+ *     S   = R + B_k^T P_{k+1} B_k                      (2 x 2)
+ *     K_k = S^-1 B_k^T P_{k+1} A_k                     (closed-form 2 x 2 inverse)
+ *     P_k = Q + A_k^T P_{k+1} (A_k - B_k K_k),  then P_k <- (P_k + P_k^T) / 2
+ * the finite-horizon discrete LQR of the deviation e_k = x_k - X_k under du_k = -K_k e_k. */
+#define NLOT_MAX_NX 8
+typedef struct NlotTvlqrOptions {
+    double q[NLOT_MAX_NX];   /* diag of Q  (state weight, knots 0..N-1), each >= 0, finite; default 1 */
+    double qf[NLOT_MAX_NX];  /* diag of Qf (knot N), each >= 0, finite; default 1 */
+    double r[NLOT_MAX_NU];   /* diag of R, each > 0, finite; default 1 */
+} NlotTvlqrOptions;          /* only the first nx / nu entries are read */
+/* Fill `opt` with the defaults documented above. */
+void nlot_default_tvlqr_options(NlotTvlqrOptions* opt);
+#define NLOT_TVLQR_NONFINITE 32  /* a non-finite entry in the instance's X or U */
+#define NLOT_TVLQR_DIVERGED 64   /* finite input, but det S <= 0 or a non-finite S, K or P at some knot */
+/* The gains of B plans of `prob`.
+ *   X [B][N+1][nx], U [B][N][nu] fp64 device (what nlot_solve_batch returns)
+ *   K      [B][N][nu][nx] fp64 device: K_k, row-major
+ *   P0     [B][nx][nx] fp64 device or NULL: P_0, the cost-to-go of a start offset d being d^T P_0 d for the
+ *          linearised loop
+ *   status [B] int32 device: 0, or NLOT_TVLQR_NONFINITE or NLOT_TVLQR_DIVERGED alone; either gives K all zero
+ *          (tracking with it is the open loop) and P0 all NaN
+ * An instance's outputs depend on that instance's inputs only: they are bitwise the same whatever B is and wherever
+ * in the batch the instance sits.
+ * Asynchronous on `stream`; no workspace, no global state (a stream-ordered temporary holds the problem).
+ * NLOT_ERR_INVALID before any device call for: a null prob, opt, X, U, K or status; an invalid problem (the checks of
+ * nlot_rollout_batch; n_obs == 0 is allowed); a q or qf entry that is negative or not finite, an r entry that is not
+ * positive or not finite (the first nx / nu entries); B outside 1 .. 2^26. */
+int32_t nlot_tvlqr_batch(const NlotProblem* prob, const NlotTvlqrOptions* opt, const double* X, const double* U,
+                         double* K, double* P0, int32_t* status, int64_t B, void* stream);
+
+typedef struct NlotTrackOptions {
+    int32_t substeps;      /* classical RK4 steps per interval, >= 1 (default 8) */
+    int32_t edge_points;   /* interior points per footprint edge, >= 0 (default 3) */
+    int32_t clamp;         /* 1 (default): the applied control is clamped to prob->umin / umax; 0: it is not */
+    int32_t pad_;
+    double clearance_min;  /* NLOT_TRACK_COLLISION if clearance < this (0) */
+    double deviation_tol;  /* NLOT_TRACK_DEVIATION if deviation > this (+inf: off) */
+    double goal_tol;       /* NLOT_TRACK_GOAL if goal_error > this (+inf: off) */
+} NlotTrackOptions;
+/* Fill `opt` with the defaults documented above. */
+void nlot_default_track_options(NlotTrackOptions* opt);
+#define NLOT_TRACK_COLLISION 1
+#define NLOT_TRACK_CONTAINS 2
+#define NLOT_TRACK_DEVIATION 4
+#define NLOT_TRACK_GOAL 8
+#define NLOT_TRACK_SATURATED 16  /* saturated > 0 */
+#define NLOT_TRACK_NONFINITE 32  /* non-finite input (X, U, K, dx0, xg) */
+#define NLOT_TRACK_DIVERGED 64   /* finite input, but an applied control or a rolled state became non-finite */
+/* nlot_rollout_batch's measurement with the loop closed.  Everything is as nlot_rollout_batch documents (poses,
+ * footprint points, clearance, where, containment, deviation, dev_where, goal_error, n_obs == 0) except:
+ *   rolled motion  starts at X[b][0] + dx0[b] (dx0 [B][nx] fp64 device; NULL: 0).  At rolled knot k < N, with state x:
+ *              e = x - X_k over all nx components (no angle is wrapped, as everywhere in this library);
+ *              u = U_k - K_k e (K [B][N][nu][nx] as nlot_tvlqr_batch writes it; NULL: u = U_k);
+ *              with opt->clamp, u_i <- min(max(u_i, umin_i), umax_i);
+ *              u is then held over the interval through `substeps` RK4 steps.  The controller is sampled at the
+ *              knots only
+ *   U_applied  [B][N][nu] fp64 device or NULL: those u
+ *   saturated  [B] int32 device: the number of knots at which the clamp changed at least one component (0 without
+ *              opt->clamp)
+ *   flags      NLOT_TRACK_* bits; 0 = passed.  A non-finite entry in the instance's X, U, K, dx0 or xg gives
+ *              NLOT_TRACK_NONFINITE alone, the three double outputs NaN and where = dev_where = saturated = -1.
+ *              Finite input from which an applied control (before the clamp) or a rolled state turns non-finite gives
+ *              NLOT_TRACK_DIVERGED alone with the same NaN / -1 outputs; X_roll and U_applied are unspecified from
+ *              that knot on
+ * With K = NULL, dx0 = NULL and clamp = 0 the rolled motion is nlot_rollout_batch's.
+ * An instance's outputs depend on that instance's inputs only: they are bitwise the same whatever B is and wherever
+ * in the batch the instance sits.
+ * Asynchronous on `stream`; no workspace, no global state (a stream-ordered temporary holds the problem).
+ * NLOT_ERR_INVALID before any device call for everything nlot_rollout_batch refuses; the required pointers are all but
+ * K, dx0, xg, X_roll and U_applied. */
+int32_t nlot_track_batch(const NlotProblem* prob, const NlotTrackOptions* opt, const double* X, const double* U,
+                         const double* K, const double* dx0, const double* xg, double* X_roll, double* U_applied,
+                         double* clearance, int32_t* where, double* deviation, int32_t* dev_where, double* goal_error,
+                         int32_t* saturated, int32_t* flags, int64_t B, void* stream);
+
 casadi_int_t nn_sdf_n_in(void);
 casadi_int_t nn_sdf_n_out(void);
 const casadi_int_t* nn_sdf_sparsity_in(casadi_int_t i);

@@ -21,6 +21,7 @@ MLP_IN_LINEAR_RELU, MLP_IN_FOURIER = 0, 1
 # hidden activations (include/nlot.h NLOT_ACT_*)
 ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_LEAKY_RELU, ACT_SINE = 0, 1, 2, 3, 4
 MAX_OBS, MAX_VERTS, MAX_BODY, MAX_NU = 128, 512, 8, 4
+MAX_NX = 8
 
 
 class NlotObstacle(C.Structure):
@@ -153,6 +154,54 @@ def rollout_options(substeps=8, edge_points=3, clearance_min=0.0, deviation_tol=
     """The defaults of nlot_default_rollout_options (the deviation and goal thresholds are off)."""
     return NlotRolloutOptions(substeps=int(substeps), edge_points=int(edge_points), clearance_min=float(clearance_min),
                               deviation_tol=float(deviation_tol), goal_tol=float(goal_tol))
+
+
+# nlot_tvlqr_batch / nlot_track_batch (include/nlot.h, ABI v19)
+TVLQR_NONFINITE, TVLQR_DIVERGED = 32, 64
+TRACK_COLLISION, TRACK_CONTAINS, TRACK_DEVIATION, TRACK_GOAL, TRACK_SATURATED, TRACK_NONFINITE, TRACK_DIVERGED = \
+    1, 2, 4, 8, 16, 32, 64
+TRACK_FLAG_NAMES = {1: "collision", 2: "contains", 4: "deviation", 8: "goal", 16: "saturated", 32: "nonfinite",
+                    64: "diverged"}
+
+
+class NlotTvlqrOptions(C.Structure):
+    """include/nlot.h NlotTvlqrOptions."""
+    _fields_ = [("q", C.c_double * MAX_NX), ("qf", C.c_double * MAX_NX), ("r", C.c_double * MAX_NU)]
+
+
+def _diag(v, n, nmax, name):
+    """A scalar or a sequence of n weights, padded with the default 1 to the struct's nmax entries."""
+    import numpy as np
+
+    a = np.asarray(v, float)
+    if a.ndim == 0:
+        a = np.full(n, float(a))
+    if a.shape != (n,):
+        raise ValueError(f"{name} must be a scalar or {n} values")
+    return list(a) + [1.0] * (nmax - n)
+
+
+def tvlqr_options(q=1.0, r=1.0, qf=1.0, nx=MAX_NX, nu=MAX_NU) -> NlotTvlqrOptions:
+    """The defaults of nlot_default_tvlqr_options (unit weights); scalars, or nx / nu values per component."""
+    o = NlotTvlqrOptions()
+    o.q[:] = _diag(q, nx, MAX_NX, "q")
+    o.qf[:] = _diag(qf, nx, MAX_NX, "qf")
+    o.r[:] = _diag(r, nu, MAX_NU, "r")
+    return o
+
+
+class NlotTrackOptions(C.Structure):
+    """include/nlot.h NlotTrackOptions."""
+    _fields_ = [("substeps", C.c_int32), ("edge_points", C.c_int32), ("clamp", C.c_int32), ("pad_", C.c_int32),
+                ("clearance_min", C.c_double), ("deviation_tol", C.c_double), ("goal_tol", C.c_double)]
+
+
+def track_options(substeps=8, edge_points=3, clamp=True, clearance_min=0.0, deviation_tol=float("inf"),
+                  goal_tol=float("inf")) -> NlotTrackOptions:
+    """The defaults of nlot_default_track_options (clamped; the deviation and goal thresholds are off)."""
+    return NlotTrackOptions(substeps=int(substeps), edge_points=int(edge_points), clamp=int(bool(clamp)), pad_=0,
+                            clearance_min=float(clearance_min), deviation_tol=float(deviation_tol),
+                            goal_tol=float(goal_tol))
 
 
 # nlot_scene_sdf_eval / nlot_sdf_metrics (include/nlot.h, ABI v18)

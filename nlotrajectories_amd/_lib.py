@@ -26,6 +26,7 @@ EXPORTED = [
     "jac_adj1_nn_sdf_n_out", "jac_adj1_nn_sdf", "nlot_rrt_workspace_size", "nlot_rrt_init",
     "nlot_default_verify_options", "nlot_verify_batch", "nlot_default_rollout_options", "nlot_rollout_batch",
     "nlot_scene_sdf_eval", "nlot_default_sdf_metrics_options", "nlot_sdf_metrics",
+    "nlot_default_tvlqr_options", "nlot_tvlqr_batch", "nlot_default_track_options", "nlot_track_batch",
 ]
 
 
@@ -95,9 +96,19 @@ def lib():
     L.nlot_default_sdf_metrics_options.restype = None
     L.nlot_sdf_metrics.argtypes = [C.POINTER(_abi.NlotSdfMetricsOptions), vp, vp, vp, C.c_int64, vp, vp]
     L.nlot_sdf_metrics.restype = C.c_int32
+    L.nlot_default_tvlqr_options.argtypes = [C.POINTER(_abi.NlotTvlqrOptions)]
+    L.nlot_default_tvlqr_options.restype = None
+    L.nlot_tvlqr_batch.argtypes = [C.POINTER(_abi.NlotProblem), C.POINTER(_abi.NlotTvlqrOptions), vp, vp, vp, vp, vp,
+                                   C.c_int64, vp]
+    L.nlot_tvlqr_batch.restype = C.c_int32
+    L.nlot_default_track_options.argtypes = [C.POINTER(_abi.NlotTrackOptions)]
+    L.nlot_default_track_options.restype = None
+    L.nlot_track_batch.argtypes = [C.POINTER(_abi.NlotProblem), C.POINTER(_abi.NlotTrackOptions), vp, vp, vp, vp, vp,
+                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp]
+    L.nlot_track_batch.restype = C.c_int32
     L.nlot_casadi_bind.argtypes = [vp]
     L.nlot_casadi_bind.restype = C.c_int32
-    if L.nlot_abi_version() != 18:
+    if L.nlot_abi_version() != 19:
         raise NlotError("libnlot.so ABI version mismatch")
     _lib = L
     return L

@@ -18,6 +18,9 @@ Differences from the reference, all loud:
     and along the footprint's edges (verify.py) and prints three more lines; nothing else changes;
   * --rollout (off by default) rolls the returned controls forward through the continuous dynamics (rollout.py:
     sub-stepped RK4, zero-order hold, open loop) and prints four more lines, after --verify's; nothing else changes;
+  * --track (off by default) computes the time-varying LQR gains about the returned plan and rolls it with the loop
+    closed (tracking.py: feedback sampled at the knots, clamped to the control bounds) and prints five more lines,
+    after --rollout's; nothing else changes;
   * --metrics-device gpu (default host) computes the SDF-quality metrics on the device (scene_gpu.scene_metrics: the
     solver's own scene functions and a brute-force nearest-neighbour kernel) instead of scene.py's numpy; the CSV is
     the same to rounding.  --train-sdf-device gpu does the same for the training targets of `--weights train`.
@@ -99,12 +102,30 @@ def _print_rollout(prob, r, xg, substeps, edge_points):
                                                   _abi.ROLLOUT_NONFINITE | _abi.ROLLOUT_DIVERGED))
 
 
+def _print_track(prob, r, xg, substeps, edge_points, q, rw, qf):
+    """--track: the plan tracked with its TVLQR gains through the continuous dynamics (tracking.py), for a failed
+    solve too."""
+    from .tracking import track_batch, tvlqr_batch
+
+    K, _, _ = tvlqr_batch(prob, r["X"], r["U"], q=q, r=rw, qf=qf)
+    v = track_batch(prob, r["X"], r["U"], K=K, xg=xg, substeps=substeps, edge_points=edge_points)
+    flags = int(v["flags"][0])
+    print(f"Tracking clearance: {float(v['clearance'][0])} at knot {int(v['where'][0]) // substeps}")
+    print(f"Tracking deviation: {float(v['deviation'][0])} at knot {int(v['dev_where'][0])}")
+    print("Tracking goal error:", float(v["goal_error"][0]))
+    print("Tracking saturated knots:", int(v["saturated"][0]))
+    print("Tracking collision-free:", not flags & (_abi.TRACK_COLLISION | _abi.TRACK_CONTAINS | _abi.TRACK_NONFINITE |
+                                                   _abi.TRACK_DIVERGED))
+
+
 def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="results", verbose=True,
                   options=None, metrics=True, verify=False, verify_sub=8, verify_edge_points=3, rollout=False,
-                  rollout_substeps=8, rollout_edge_points=3, metrics_device="host", train_sdf_device="host"):
+                  rollout_substeps=8, rollout_edge_points=3, metrics_device="host", train_sdf_device="host",
+                  track=False, track_substeps=8, track_edge_points=3, track_q=1.0, track_r=1.0, track_qf=1.0):
     """Returns (X_opt [nx, N+1], U_opt [nu, N], status str) like RunBenchmark.run (runner.py:148-153).
     verify=True also prints the trajectory's exact clearance, dynamics defect and collision verdict; rollout=True the
-    clearance, deviation from the plan and goal error of the controls rolled through the continuous dynamics."""
+    clearance, deviation from the plan and goal error of the controls rolled through the continuous dynamics;
+    track=True the same and the saturated knots of the plan tracked with its TVLQR gains."""
     config_path = Path(config_path)
     cfg = Config.load(config_path)
     if cfg.solver.type != "ipopt":
@@ -156,6 +177,8 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
                 _print_verification(prob, r, x0, xg, verify_sub, verify_edge_points)
             if rollout:
                 _print_rollout(prob, r, xg, rollout_substeps, rollout_edge_points)
+            if track:
+                _print_track(prob, r, xg, track_substeps, track_edge_points, track_q, track_r, track_qf)
         return X, U, status
     obj = float(r["cost"][0])
     if not verbose:
@@ -171,6 +194,8 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
         _print_verification(prob, r, x0, xg, verify_sub, verify_edge_points)
     if rollout:
         _print_rollout(prob, r, xg, rollout_substeps, rollout_edge_points)
+    if track:
+        _print_track(prob, r, xg, track_substeps, track_edge_points, track_q, track_r, track_qf)
     out = Path(results_dir)
     out.mkdir(parents=True, exist_ok=True)
     f = out / f"{config_path.stem}_results.csv"
@@ -226,6 +251,16 @@ def _parser():
                          "open loop) and report the rolled motion's clearance, deviation and goal error (rollout.py)")
     ap.add_argument("--rollout-substeps", type=int, default=8, help="--rollout: RK4 steps per interval")
     ap.add_argument("--rollout-edge-points", type=int, default=3, help="--rollout: interior points per footprint edge")
+    ap.add_argument("--track", action="store_true",
+                    help="track the returned plan with its time-varying LQR gains through the continuous dynamics "
+                         "(feedback at the knots, clamped to the control bounds) and report the closed loop's clearance, "
+                         "deviation, goal error and saturated knots (tracking.py)")
+    ap.add_argument("--track-substeps", type=int, default=8, help="--track: RK4 steps per interval")
+    ap.add_argument("--track-edge-points", type=int, default=3, help="--track: interior points per footprint edge")
+    ap.add_argument("--track-q", type=float, nargs="+", default=[1.0],
+                    help="--track: state weight at knots 0..N-1, one value for every component or one per component")
+    ap.add_argument("--track-r", type=float, nargs="+", default=[1.0], help="--track: control weight, likewise")
+    ap.add_argument("--track-qf", type=float, nargs="+", default=[1.0], help="--track: state weight at the last knot")
     ap.add_argument("--metrics-device", choices=["host", "gpu"], default="host",
                     help="where the SDF-quality metrics are computed: numpy (scene.py) or the GPU (scene_gpu.py)")
     ap.add_argument("--train-sdf-device", choices=["host", "gpu"], default="host",
@@ -233,12 +268,19 @@ def _parser():
     return ap
 
 
+def _weight(values):
+    """One value: a scalar for every component; more: one per component (tracking.tvlqr_batch checks the count)."""
+    return values[0] if len(values) == 1 else tuple(values)
+
+
 def main(argv=None):
     a = _parser().parse_args(argv)
     run_benchmark(Path(a.config), initializer=a.initializer, weights=a.weights, results_dir=a.results, verify=a.verify,
                   verify_sub=a.verify_sub, verify_edge_points=a.verify_edge_points, rollout=a.rollout,
                   rollout_substeps=a.rollout_substeps, rollout_edge_points=a.rollout_edge_points,
-                  metrics_device=a.metrics_device, train_sdf_device=a.train_sdf_device)
+                  metrics_device=a.metrics_device, train_sdf_device=a.train_sdf_device, track=a.track,
+                  track_substeps=a.track_substeps, track_edge_points=a.track_edge_points, track_q=_weight(a.track_q),
+                  track_r=_weight(a.track_r), track_qf=_weight(a.track_qf))
 
 
 if __name__ == "__main__":

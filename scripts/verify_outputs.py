@@ -12,6 +12,11 @@ instances with flags == 0, the shares per flag, and the clearance quantiles of t
 and adds one key `rollout`: the shares per rollout flag, the quantiles of the deviation from the plan, of the goal
 error (against the plan's last knot: the dump carries no goals) and of the rolled clearance over the solved instances,
 and how many of the instances verify_batch passes the rollout flags.
+
+--track [--track-substeps 8 --track-q 1 --track-r 1 --track-qf 1] (each weight one value, or one per component) also computes the TVLQR gains about every dumped plan
+(nlot_tvlqr_batch) and rolls it with the loop closed (nlot_track_batch); it adds one key `track` with the same fields
+as `rollout` for the closed loop, the share of the solved instances that saturate, the quantiles of the saturated-knot
+count, and the gains' status counts.
 """
 import argparse
 import json
@@ -42,7 +47,15 @@ def main(argv=None):
     ap.add_argument("--edge-points", type=int, default=3)
     ap.add_argument("--rollout", action="store_true", help="also roll the controls through the dynamics (rollout_batch)")
     ap.add_argument("--rollout-substeps", type=int, default=8)
+    ap.add_argument("--track", action="store_true", help="also track the plans with their TVLQR gains (track_batch)")
+    ap.add_argument("--track-substeps", type=int, default=8)
+    ap.add_argument("--track-q", type=float, nargs="+", default=[1.0], help="one value, or one per state component")
+    ap.add_argument("--track-r", type=float, nargs="+", default=[1.0], help="one value, or one per control")
+    ap.add_argument("--track-qf", type=float, nargs="+", default=[1.0], help="one value, or one per state component")
     a = ap.parse_args(argv)
+    for k in ("track_q", "track_r", "track_qf"):  # one value: a scalar for every component
+        v = getattr(a, k)
+        setattr(a, k, v[0] if len(v) == 1 else v)
 
     from nlotrajectories_amd import _abi
     from nlotrajectories_amd.problem import METRIC_PROBLEM, STRESS_PROBLEM
@@ -78,6 +91,28 @@ def main(argv=None):
                               deviation_quantiles=quant("deviation"), goal_error_quantiles=quant("goal_error"),
                               clearance_quantiles=quant("clearance"), verify_ok=int((flags == 0).sum()),
                               verify_ok_rollout_flagged=int(((flags == 0) & (rflags != 0)).sum()))
+    if a.track:
+        from nlotrajectories_amd.tracking import track_batch, tvlqr_batch
+
+        K, _, kst = tvlqr_batch(prob, X, U, q=a.track_q, r=a.track_r, qf=a.track_qf)
+        t = track_batch(prob, X, U, K=K, obstacles=scene_obstacles(a.scene), substeps=a.track_substeps,
+                        edge_points=a.edge_points)
+        tflags, kst = t["flags"].cpu().numpy()[solved], kst.cpu().numpy()[solved]
+        sat = t["saturated"].cpu().numpy()[solved]
+        qs = (0.0, 0.01, 0.1, 0.5, 0.9, 1.0)
+        quant = lambda k: {str(q): float(np.nanquantile(t[k].cpu().numpy()[solved], q)) if n else None for q in qs}  # noqa: E731
+        hits = _abi.TRACK_COLLISION | _abi.TRACK_CONTAINS
+        out["track"] = dict(substeps=a.track_substeps, q=a.track_q, r=a.track_r, qf=a.track_qf,
+                            gains_nonfinite=int((kst == _abi.TVLQR_NONFINITE).sum()),
+                            gains_diverged=int((kst == _abi.TVLQR_DIVERGED).sum()),
+                            flag_shares={name: float(((tflags & bit) != 0).mean()) if n else None
+                                         for bit, name in _abi.TRACK_FLAG_NAMES.items()},
+                            deviation_quantiles=quant("deviation"), goal_error_quantiles=quant("goal_error"),
+                            clearance_quantiles=quant("clearance"),
+                            saturated_share=float((sat > 0).mean()) if n else None,
+                            saturated_knots_quantiles={str(q): float(np.quantile(sat, q)) if n else None for q in qs},
+                            verify_ok=int((flags == 0).sum()),
+                            verify_ok_track_collides=int(((flags == 0) & ((tflags & hits) != 0)).sum()))
     print(json.dumps(out))
 
 
