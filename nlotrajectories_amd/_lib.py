@@ -131,3 +131,41 @@ def stream_ptr(stream=None):
 
     s = stream if stream is not None else torch.cuda.current_stream()
     return C.c_void_p(s.cuda_stream)
+
+
+def ptr(t):
+    """The data pointer of tensor `t` as an argument of the library (None: NULL)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def plan_tensors(problem, X, U, device, *extras):
+    """B plans of `problem` as contiguous fp64 tensors on `device`: X [B, N+1, nx], U [B, N, nu] and the optional
+    per-instance inputs `extras`, each (name, array or None, shape after B).  Returns (X, U, B, *extras), a None
+    extra staying None; a wrong shape raises ValueError."""
+    import torch
+
+    f64 = dict(dtype=torch.float64, device=device)
+    X = torch.as_tensor(X, **f64).contiguous()
+    U = torch.as_tensor(U, **f64).contiguous()
+    if X.dim() != 3 or X.shape[1:] != (problem.N + 1, problem.nx):
+        raise ValueError(f"X must be [B, {problem.N + 1}, {problem.nx}]")
+    B = X.shape[0]
+    if U.shape != (B, problem.N, problem.nu):
+        raise ValueError(f"U must be [{B}, {problem.N}, {problem.nu}]")
+    out = []
+    for name, t, shape in extras:
+        if t is not None:
+            t = torch.as_tensor(t, **f64).contiguous()
+            if t.shape != (B, *shape):
+                raise ValueError(f"{name} must be [{', '.join(map(str, (B, *shape)))}]")
+        out.append(t)
+    return (X, U, B, *out)
+
+
+def scene_problem(problem, obstacles=None):
+    """The NlotProblem a measurement against the exact scene passes: `problem` with the scene `obstacles` (None: its
+    own), or with n_obs == 0 when there is none."""
+    scene = problem.obstacles if obstacles is None else obstacles
+    if scene:
+        return problem.with_(sdf="analytic", obstacles=list(scene)).to_c()  # to_c() drops the scene of an mlp problem
+    return problem.with_(sdf="mlp", obstacles=[]).to_c()

@@ -1,7 +1,9 @@
-// C-ABI plumbing of libnlot.so: version, thread-local errors, defaults, and the CasADi external
+// C-ABI plumbing of libnlot.so: version, thread-local errors, the problem checks the measurement entry points share
+// (check_problem, check_sample_count of nlot_internal.h), defaults, and the CasADi external
 // compatibility shim (gen/nn_sdf.cpp:36-104 signatures).
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -11,6 +13,46 @@
 namespace nlot {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
+
+bool check_problem(const NlotProblem* prob, int64_t B, const char* who) {
+    static const int kNx[6] = {4, 4, 3, 5, 4, 7};
+    const std::string w(who);
+    if (prob->dynamics < 0 || prob->dynamics > NLOT_ACKERMANN_2ND || prob->nx != kNx[prob->dynamics] || prob->nu != 2 ||
+        prob->N < 1 || prob->N > 1 << 24 || prob->n_obs < 0 || prob->n_obs > NLOT_MAX_OBS || prob->n_verts < 0 ||
+        prob->n_verts > NLOT_MAX_VERTS || (prob->shape != NLOT_SHAPE_DOT && prob->shape != NLOT_SHAPE_POLYGON) ||
+        (prob->shape == NLOT_SHAPE_POLYGON && (prob->n_body < 1 || prob->n_body > NLOT_MAX_BODY))) {
+        set_error(w + ": invalid problem (dynamics, nx / nu, 1 <= N <= 2^24, shape, n_body, n_obs, n_verts)");
+        return false;
+    }
+    for (int i = 0; i < prob->n_obs; ++i) {
+        const NlotObstacle& q = prob->obs[i];
+        if (q.type < NLOT_OBS_CIRCLE || q.type > NLOT_OBS_TRAPEZOID) {
+            set_error(w + ": unknown obstacle type");
+            return false;
+        }
+        if ((q.type == NLOT_OBS_POLYGON || q.type == NLOT_OBS_TRAPEZOID) &&
+            (q.v0 < 0 || q.nv < 2 || q.v0 > prob->n_verts - q.nv)) {
+            set_error(w + ": polygon vertex range outside verts[0, n_verts)");
+            return false;
+        }
+    }
+    if (B < 1 || B > (int64_t)1 << 26) {
+        set_error(w + ": B out of range");
+        return false;
+    }
+    return true;
+}
+
+bool check_sample_count(const NlotProblem* prob, int substeps, int edge_points, const char* who, const char* name) {
+    // the kernels count poses, footprint points and (k_verify) their product with ints
+    const int64_t P = (int64_t)prob->N * substeps + 1;
+    const int64_t npp = prob->shape == NLOT_SHAPE_POLYGON ? (int64_t)prob->n_body * (1 + (int64_t)edge_points) : 1;
+    if (P > INT32_MAX || npp > INT32_MAX || P * npp > INT32_MAX - 64) {
+        set_error(std::string(who) + ": sample count (N " + name + " + 1) * n_body (1 + edge_points) overflows int32");
+        return false;
+    }
+    return true;
+}
 }  // namespace nlot
 
 extern "C" int32_t nlot_abi_version(void) { return NLOT_ABI_VERSION; }

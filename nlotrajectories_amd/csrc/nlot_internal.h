@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "../../include/nlot.h"
 
@@ -26,6 +27,44 @@ void set_error(const std::string& msg);
             return NLOT_ERR_HIP;                                                                   \
         }                                                                                          \
     } while (0)
+
+// What nlot_verify_batch, nlot_rollout_batch, nlot_tvlqr_batch and nlot_track_batch require of the problem and of B,
+// and of the int32 sample count (N `substeps` + 1) * n_body (1 + edge_points) the first, second and last index with
+// (`name` is how the caller's message spells its sub-step option).  False after set_error("`who`: ...")
+// (nlot_capi.hip).
+bool check_problem(const NlotProblem* prob, int64_t B, const char* who);
+bool check_sample_count(const NlotProblem* prob, int substeps, int edge_points, const char* who, const char* name);
+
+// f(std::integral_constant<int, D>{}) for the dynamics model D = id (validated by the caller)
+template <class F>
+__host__ __device__ inline auto dispatch_dynamics(int id, F&& f) {
+    switch (id) {
+        case NLOT_POINT_1ST: return f(std::integral_constant<int, NLOT_POINT_1ST>{});
+        case NLOT_POINT_2ND: return f(std::integral_constant<int, NLOT_POINT_2ND>{});
+        case NLOT_UNICYCLE: return f(std::integral_constant<int, NLOT_UNICYCLE>{});
+        case NLOT_UNICYCLE_2ND: return f(std::integral_constant<int, NLOT_UNICYCLE_2ND>{});
+        case NLOT_ACKERMANN: return f(std::integral_constant<int, NLOT_ACKERMANN>{});
+        default: return f(std::integral_constant<int, NLOT_ACKERMANN_2ND>{});
+    }
+}
+
+// Kernels read the problem through a pointer (it is larger than the kernel-argument area): launch(dP) runs with a
+// stream-ordered device copy that lives for this call only, so no workspace argument and no global state.  Returns
+// the first HIP error of the copy, the launch and the free.
+template <class F>
+int32_t with_device_problem(const NlotProblem* prob, hipStream_t st, F&& launch) {
+    NlotProblem* dP = nullptr;
+    NLOT_HIP_CHECK(hipMallocAsync((void**)&dP, sizeof(NlotProblem), st));
+    hipError_t e = hipMemcpyAsync(dP, prob, sizeof(NlotProblem), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        launch(dP);
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(dP, st);
+    NLOT_HIP_CHECK(e);
+    NLOT_HIP_CHECK(ef);
+    return NLOT_OK;
+}
 
 // One-time per-device kernel attribute (the dynamic-LDS limit): `done` is a bit mask over device ids
 // kept per kernel instantiation, so a process driving several GPUs sets it on each of them, and

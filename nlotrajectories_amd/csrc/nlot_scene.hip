@@ -331,10 +331,7 @@ extern "C" int32_t nlot_scene_sdf_eval(const NlotProblem* prob, int32_t kind, co
         return NLOT_ERR_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
-    NlotProblem* dP = nullptr;
-    NLOT_HIP_CHECK(hipMallocAsync((void**)&dP, sizeof(NlotProblem), st));
-    hipError_t e = hipMemcpyAsync(dP, prob, sizeof(NlotProblem), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+    return with_device_problem(prob, st, [&](const NlotProblem* dP) {
         const int64_t want = (P + kEvalThreads - 1) / kEvalThreads, cap = (int64_t)device_cus() * 16;
         const dim3 grid((unsigned)(want < cap ? want : cap)), block(kEvalThreads);
         if (kind == NLOT_SCENE_EXACT)
@@ -343,12 +340,7 @@ extern "C" int32_t nlot_scene_sdf_eval(const NlotProblem* prob, int32_t kind, co
             hipLaunchKernelGGL((k_scene_eval<NLOT_SCENE_APPROX, true>), grid, block, 0, st, dP, pts, P, val, grad, hess);
         else
             hipLaunchKernelGGL((k_scene_eval<NLOT_SCENE_APPROX, false>), grid, block, 0, st, dP, pts, P, val, grad, hess);
-        e = hipGetLastError();
-    }
-    const hipError_t ef = hipFreeAsync(dP, st);
-    NLOT_HIP_CHECK(e);
-    NLOT_HIP_CHECK(ef);
-    return NLOT_OK;
+    });
 }
 
 extern "C" void nlot_default_sdf_metrics_options(NlotSdfMetricsOptions* opt) {

@@ -12,21 +12,13 @@
 //     values.
 // The obstacle data is read through the kernel's NlotProblem pointer with wave-uniform indices, i.e. on the
 // scalar-load path, as k_rrt does.
-#include <climits>
-#include <cmath>
-
-#include "nlot_device.h"
-#include "nlot_internal.h"
+#include "nlot_roll.h"
 
 namespace nlot {
 namespace {
 
 constexpr int kWavesPerBlock = 4;
 
-__device__ inline int wave_or(int v) {
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
 __device__ inline double wave_max(double v) {
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
     return v;
@@ -50,20 +42,11 @@ __device__ double interval_defect(const NlotProblem& p, const double* xk, const 
 }
 
 __device__ double interval_defect_any(const NlotProblem& p, const double* xk, const double* xk1, const double* uk) {
-    switch (p.dynamics + (p.integrator == NLOT_INTEG_RK4 ? NLOT_RK4_BIAS : 0)) {
-        case NLOT_POINT_1ST: return interval_defect<NLOT_POINT_1ST>(p, xk, xk1, uk);
-        case NLOT_POINT_2ND: return interval_defect<NLOT_POINT_2ND>(p, xk, xk1, uk);
-        case NLOT_UNICYCLE: return interval_defect<NLOT_UNICYCLE>(p, xk, xk1, uk);
-        case NLOT_UNICYCLE_2ND: return interval_defect<NLOT_UNICYCLE_2ND>(p, xk, xk1, uk);
-        case NLOT_ACKERMANN: return interval_defect<NLOT_ACKERMANN>(p, xk, xk1, uk);
-        case NLOT_ACKERMANN_2ND: return interval_defect<NLOT_ACKERMANN_2ND>(p, xk, xk1, uk);
-        case NLOT_POINT_1ST + NLOT_RK4_BIAS: return interval_defect<NLOT_POINT_1ST + NLOT_RK4_BIAS>(p, xk, xk1, uk);
-        case NLOT_POINT_2ND + NLOT_RK4_BIAS: return interval_defect<NLOT_POINT_2ND + NLOT_RK4_BIAS>(p, xk, xk1, uk);
-        case NLOT_UNICYCLE + NLOT_RK4_BIAS: return interval_defect<NLOT_UNICYCLE + NLOT_RK4_BIAS>(p, xk, xk1, uk);
-        case NLOT_UNICYCLE_2ND + NLOT_RK4_BIAS: return interval_defect<NLOT_UNICYCLE_2ND + NLOT_RK4_BIAS>(p, xk, xk1, uk);
-        case NLOT_ACKERMANN + NLOT_RK4_BIAS: return interval_defect<NLOT_ACKERMANN + NLOT_RK4_BIAS>(p, xk, xk1, uk);
-        default: return interval_defect<NLOT_ACKERMANN_2ND + NLOT_RK4_BIAS>(p, xk, xk1, uk);
-    }
+    if (p.integrator == NLOT_INTEG_RK4)
+        return dispatch_dynamics(p.dynamics, [&](auto d) {
+            return interval_defect<decltype(d)::value + NLOT_RK4_BIAS>(p, xk, xk1, uk);
+        });
+    return dispatch_dynamics(p.dynamics, [&](auto d) { return interval_defect<decltype(d)::value>(p, xk, xk1, uk); });
 }
 
 // pose s of the P = N sub + 1 sampled ones: x_k + tau (x_{k+1} - x_k), k = s / sub, tau = (s mod sub) / sub; the
@@ -105,7 +88,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_verify(
     if (x0) {
         for (int i = lane; i < nx; i += 64) bad |= !isfinite(x0[b * nx + i]) || !isfinite(xg[b * nx + i]);
     }
-    if (wave_or(bad)) {
+    if (group_or<64>(bad)) {
         if (lane == 0) {
             clearance[b] = defect[b] = ubound[b] = boundary[b] = NAN;
             where[b] = -1;
@@ -127,20 +110,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_verify(
         double px, py, th;
         sample_pose(X, nx, N, sub, s, poly, &px, &py, &th);
         double wx = px, wy = py;
-        if (poly) {  // PolygonGeometry.transform of corners i, i + 1, then densify_polygon's (1 - t) p0 + t p1
-            const int i = j / per_edge, m = j - i * per_edge, i1 = i + 1 < p.n_body ? i + 1 : 0;
+        if (poly) {
             double sn, cs;
             sincos(th, &sn, &cs);
-            const double ax = px + cs * p.body[i][0] - sn * p.body[i][1], ay = py + sn * p.body[i][0] + cs * p.body[i][1];
-            wx = ax;
-            wy = ay;
-            if (m > 0) {
-                const double bx = px + cs * p.body[i1][0] - sn * p.body[i1][1];
-                const double by = py + sn * p.body[i1][0] + cs * p.body[i1][1];
-                const double t = (double)m / (double)per_edge;
-                wx = (1.0 - t) * ax + t * bx;
-                wy = (1.0 - t) * ay + t * by;
-            }
+            footprint_point(p, px, py, sn, cs, j, per_edge, &wx, &wy);
         }
         const double v = exact_sdf(p, wx, wy);
         if (v < best) {  // s ascends within a lane: the first pose of the lane's minimum
@@ -148,14 +121,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_verify(
             bs = s;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(best, off);
-        const int os = __shfl_xor(bs, off);
-        if (ov < best || (ov == best && os < bs)) {
-            best = ov;
-            bs = os;
-        }
-    }
+    group_argmin<64>(best, bs);
 
     // containment: an obstacle smaller than the footprint can sit inside it with every perimeter point outside
     int contains = 0;
@@ -164,20 +130,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_verify(
             double px, py, th, sn, cs;
             sample_pose(X, nx, N, sub, s, true, &px, &py, &th);
             sincos(th, &sn, &cs);
-            for (int i = 0; i < p.n_obs; ++i) {
-                const NlotObstacle& q = p.obs[i];
-                if (q.type == NLOT_OBS_CIRCLE || q.type == NLOT_OBS_SQUARE) {
-                    const double dx = q.cx - px, dy = q.cy - py;
-                    contains |= inside_body(p, cs * dx + sn * dy, -sn * dx + cs * dy);
-                } else {
-                    for (int e = 0; e < q.nv; ++e) {
-                        const double dx = p.verts[q.v0 + e][0] - px, dy = p.verts[q.v0 + e][1] - py;
-                        contains |= inside_body(p, cs * dx + sn * dy, -sn * dx + cs * dy);
-                    }
-                }
-            }
+            obstacles_inside_body(p, px, py, sn, cs, 0, 1, contains);
         }
-        contains = wave_or(contains);
+        contains = group_or<64>(contains);
     }
 
     // residuals
@@ -232,7 +187,6 @@ extern "C" int32_t nlot_verify_batch(const NlotProblem* prob, const NlotVerifyOp
                                      int32_t* where, double* defect, double* ubound, double* boundary, int32_t* flags,
                                      int64_t B, void* stream) {
     using namespace nlot;
-    static const int kNx[6] = {4, 4, 3, 5, 4, 7};
     if (!prob || !opt) {
         set_error("nlot_verify_batch: null problem or options");
         return NLOT_ERR_INVALID;
@@ -249,37 +203,9 @@ extern "C" int32_t nlot_verify_batch(const NlotProblem* prob, const NlotVerifyOp
         set_error("nlot_verify_batch: the problem carries no scene (n_obs == 0)");
         return NLOT_ERR_INVALID;
     }
-    if (prob->dynamics < 0 || prob->dynamics > NLOT_ACKERMANN_2ND || prob->nx != kNx[prob->dynamics] || prob->nu != 2 ||
-        prob->N < 1 || prob->N > 1 << 24 || prob->n_obs < 0 || prob->n_obs > NLOT_MAX_OBS || prob->n_verts < 0 ||
-        prob->n_verts > NLOT_MAX_VERTS || (prob->shape != NLOT_SHAPE_DOT && prob->shape != NLOT_SHAPE_POLYGON) ||
-        (prob->shape == NLOT_SHAPE_POLYGON && (prob->n_body < 1 || prob->n_body > NLOT_MAX_BODY))) {
-        set_error("nlot_verify_batch: invalid problem (dynamics, nx / nu, 1 <= N <= 2^24, shape, n_body, n_obs, n_verts)");
+    if (!check_problem(prob, B, "nlot_verify_batch") ||
+        !check_sample_count(prob, opt->sub, opt->edge_points, "nlot_verify_batch", "sub"))
         return NLOT_ERR_INVALID;
-    }
-    for (int i = 0; i < prob->n_obs; ++i) {
-        const NlotObstacle& q = prob->obs[i];
-        if (q.type < NLOT_OBS_CIRCLE || q.type > NLOT_OBS_TRAPEZOID) {
-            set_error("nlot_verify_batch: unknown obstacle type");
-            return NLOT_ERR_INVALID;
-        }
-        if ((q.type == NLOT_OBS_POLYGON || q.type == NLOT_OBS_TRAPEZOID) &&
-            (q.v0 < 0 || q.nv < 2 || q.v0 > prob->n_verts - q.nv)) {
-            set_error("nlot_verify_batch: polygon vertex range outside verts[0, n_verts)");
-            return NLOT_ERR_INVALID;
-        }
-    }
-    if (B < 1 || B > (int64_t)1 << 26) {
-        set_error("nlot_verify_batch: B out of range");
-        return NLOT_ERR_INVALID;
-    }
-    {  // the kernel indexes the (pose, footprint point) samples of an instance with an int
-        const int64_t P = (int64_t)prob->N * opt->sub + 1;
-        const int64_t npp = prob->shape == NLOT_SHAPE_POLYGON ? (int64_t)prob->n_body * (1 + (int64_t)opt->edge_points) : 1;
-        if (P > INT32_MAX || npp > INT32_MAX || P * npp > INT32_MAX - 64) {
-            set_error("nlot_verify_batch: sample count (N sub + 1) * n_body (1 + edge_points) overflows int32");
-            return NLOT_ERR_INVALID;
-        }
-    }
     if ((x0 == nullptr) != (xg == nullptr)) {
         set_error("nlot_verify_batch: x0 and xg must both be given or both be NULL");
         return NLOT_ERR_INVALID;
@@ -288,20 +214,10 @@ extern "C" int32_t nlot_verify_batch(const NlotProblem* prob, const NlotVerifyOp
         set_error("nlot_verify_batch: null pointer");
         return NLOT_ERR_INVALID;
     }
-    // the kernel reads the problem through a pointer (it is larger than the kernel-argument area): a stream-ordered
-    // device copy that lives for this call only — no workspace argument, no global state
     hipStream_t st = (hipStream_t)stream;
-    NlotProblem* dP = nullptr;
-    NLOT_HIP_CHECK(hipMallocAsync((void**)&dP, sizeof(NlotProblem), st));
-    hipError_t e = hipMemcpyAsync(dP, prob, sizeof(NlotProblem), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+    return with_device_problem(prob, st, [&](const NlotProblem* dP) {
         const unsigned grid = (unsigned)((B + kWavesPerBlock - 1) / kWavesPerBlock);
         hipLaunchKernelGGL(k_verify, dim3(grid), dim3(64 * kWavesPerBlock), 0, st, dP, *opt, X, U, x0, xg, clearance,
                            where, defect, ubound, boundary, flags, B);
-        e = hipGetLastError();
-    }
-    const hipError_t ef = hipFreeAsync(dP, st);
-    NLOT_HIP_CHECK(e);
-    NLOT_HIP_CHECK(ef);
-    return NLOT_OK;
+    });
 }

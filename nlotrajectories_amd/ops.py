@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._lib import check, lib, require_gpu, stream_ptr
+from ._lib import check, lib, ptr, require_gpu, stream_ptr
 from .nn import MlpWeights
 
 
@@ -43,10 +43,6 @@ class DeviceMlp:
             self.handle = None
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def sdf_mlp_eval(mlp: DeviceMlp, pts: torch.Tensor, lam: torch.Tensor = None, derivatives: bool = True):
     """nn_sdf family on the GPU: pts [P,2] fp32 cuda -> (val [P], lam*grad [P,2], lam*hess [P,2,2]).
 
@@ -62,6 +58,6 @@ def sdf_mlp_eval(mlp: DeviceMlp, pts: torch.Tensor, lam: torch.Tensor = None, de
         hess = torch.empty(P, 2, 2, device=pts.device, dtype=torch.float32)
     if lam is not None:
         lam = lam.to(device=pts.device, dtype=torch.float32).contiguous()
-    check(lib().nlot_sdf_mlp_eval(mlp.handle, _ptr(pts), P, _ptr(val), _ptr(grad), _ptr(lam), _ptr(hess),
+    check(lib().nlot_sdf_mlp_eval(mlp.handle, ptr(pts), P, ptr(val), ptr(grad), ptr(lam), ptr(hess),
                                   stream_ptr()), "nlot_sdf_mlp_eval")
     return val, grad, hess

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._lib import check, lib, require_gpu, stream_ptr
+from ._lib import check, lib, ptr, require_gpu, scene_problem, stream_ptr
 from .problem import Problem
 
 KINDS = {"exact": _abi.SCENE_EXACT, "approx": _abi.SCENE_APPROX}
@@ -23,22 +23,17 @@ KINDS = {"exact": _abi.SCENE_EXACT, "approx": _abi.SCENE_APPROX}
 NEAREST_TILE = 1024
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _scene_problem(obstacles_or_problem) -> Problem:
-    """A Problem whose to_c() carries the scene: the given one, or a dot body around bare obstacle dicts (only the
-    scene fields are read).  A learned-SDF problem is switched to analytic, as verify_batch does."""
+def _scene_problem(obstacles_or_problem):
+    """An NlotProblem that carries the scene: the given Problem's (verify_batch's), or a dot body around bare
+    obstacle dicts (only the scene fields are read)."""
     if isinstance(obstacles_or_problem, Problem):
-        scene = obstacles_or_problem.obstacles
-        if not scene:
+        if not obstacles_or_problem.obstacles:
             raise ValueError("scene_sdf_eval: the problem has no obstacles")
-        return obstacles_or_problem.with_(sdf="analytic", obstacles=list(scene))
+        return scene_problem(obstacles_or_problem)
     scene = list(obstacles_or_problem)
     if not scene:
         raise ValueError("scene_sdf_eval: no obstacles")
-    return Problem(dynamics="point_2nd", shape="dot", sdf="analytic", obstacles=scene)
+    return Problem(dynamics="point_2nd", shape="dot", sdf="analytic", obstacles=scene).to_c()
 
 
 def _points(pts):
@@ -63,7 +58,7 @@ def scene_sdf_eval(obstacles_or_problem, pts, kind="exact", derivatives=False, d
     if derivatives and kind == "exact":
         raise ValueError("derivatives need kind='approx': the exact SDF has no derivative code")
     pts = _points(pts)
-    pc = _scene_problem(obstacles_or_problem).to_c()
+    pc = _scene_problem(obstacles_or_problem)
     require_gpu()
     f64 = dict(dtype=torch.float64, device=device)
     pts = _device(pts, **f64)
@@ -71,7 +66,7 @@ def scene_sdf_eval(obstacles_or_problem, pts, kind="exact", derivatives=False, d
     val = torch.empty(P, **f64)
     grad = torch.empty(P, 2, **f64) if derivatives else None
     hess = torch.empty(P, 3, **f64) if derivatives else None
-    check(lib().nlot_scene_sdf_eval(C.byref(pc), KINDS[kind], _ptr(pts), P, _ptr(val), _ptr(grad), _ptr(hess),
+    check(lib().nlot_scene_sdf_eval(C.byref(pc), KINDS[kind], ptr(pts), P, ptr(val), ptr(grad), ptr(hess),
                                     stream_ptr()), "nlot_scene_sdf_eval")
     return (val, grad, hess) if derivatives else val
 
@@ -93,7 +88,7 @@ def sdf_metrics(pts, target, pred, threshold=0.0, eps=1e-2, device="cuda"):
     pts, target, pred = _device(pts, **f64), _device(target, **f64).reshape(-1), _device(pred, **f64).reshape(-1)
     out = torch.empty(C.sizeof(_abi.NlotSdfMetrics), dtype=torch.uint8, device=pts.device)
     opt = _abi.sdf_metrics_options(threshold, eps)
-    check(lib().nlot_sdf_metrics(C.byref(opt), _ptr(pts), _ptr(target), _ptr(pred), P, _ptr(out), stream_ptr()),
+    check(lib().nlot_sdf_metrics(C.byref(opt), ptr(pts), ptr(target), ptr(pred), P, ptr(out), stream_ptr()),
           "nlot_sdf_metrics")
     m = _abi.NlotSdfMetrics.from_buffer_copy(out.cpu().numpy().tobytes())
     r = {k: getattr(m, k) for k, _ in m._fields_}

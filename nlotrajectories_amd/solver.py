@@ -12,13 +12,9 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._lib import check, lib, require_gpu, stream_ptr
+from ._lib import check, lib, ptr, require_gpu, stream_ptr
 from .ops import DeviceMlp
 from .problem import Problem
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def solve_batch(problem: Problem, x0, xg, mlp: Optional[DeviceMlp] = None, options=None, X_init=None,
@@ -53,9 +49,9 @@ def solve_batch(problem: Problem, x0, xg, mlp: Optional[DeviceMlp] = None, optio
     nbytes = lib().nlot_solve_workspace_size_slots(C.byref(pc), B, int(opt.max_active))
     if workspace is None or workspace.numel() < nbytes:
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    check(lib().nlot_solve_batch(C.byref(pc), C.byref(opt), mlp.handle if mlp is not None else None, _ptr(x0),
-                                 _ptr(xg), _ptr(Xi), _ptr(X), _ptr(U), _ptr(S), _ptr(cost), _ptr(status),
-                                 _ptr(iters), B, _ptr(workspace), nbytes, stream_ptr()), "nlot_solve_batch")
+    check(lib().nlot_solve_batch(C.byref(pc), C.byref(opt), mlp.handle if mlp is not None else None, ptr(x0),
+                                 ptr(xg), ptr(Xi), ptr(X), ptr(U), ptr(S), ptr(cost), ptr(status),
+                                 ptr(iters), B, ptr(workspace), nbytes, stream_ptr()), "nlot_solve_batch")
     return dict(X=X, U=U, S=S, cost=cost, status=status, iters=iters)
 
 

@@ -17,23 +17,8 @@ import math
 import torch
 
 from . import _abi
-from ._lib import check, lib, require_gpu, stream_ptr
+from ._lib import check, lib, plan_tensors, ptr, require_gpu, scene_problem, stream_ptr
 from .problem import Problem
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _plan(problem, X, U, f64):
-    X = torch.as_tensor(X, **f64).contiguous()
-    U = torch.as_tensor(U, **f64).contiguous()
-    if X.dim() != 3 or X.shape[1:] != (problem.N + 1, problem.nx):
-        raise ValueError(f"X must be [B, {problem.N + 1}, {problem.nx}]")
-    B = X.shape[0]
-    if U.shape != (B, problem.N, problem.nu):
-        raise ValueError(f"U must be [{B}, {problem.N}, {problem.nu}]")
-    return X, U, B
 
 
 def tvlqr_batch(problem: Problem, X, U, q=1.0, r=1.0, qf=1.0, device="cuda"):
@@ -43,14 +28,14 @@ def tvlqr_batch(problem: Problem, X, U, q=1.0, r=1.0, qf=1.0, device="cuda"):
     or nx / nu values.  Returns (K [B, N, nu, nx], P0 [B, nx, nx], status [B] int32): status is 0 or
     _abi.TVLQR_NONFINITE / TVLQR_DIVERGED, both of which give K = 0 (the open loop) and P0 = NaN."""
     require_gpu()
-    pc = problem.with_(sdf="mlp", obstacles=[]).to_c()  # the gains do not see the scene
+    pc = scene_problem(problem, obstacles=[])  # the gains do not see the scene
     opt = _abi.tvlqr_options(q, r, qf, nx=problem.nx, nu=problem.nu)
     f64 = dict(dtype=torch.float64, device=device)
-    X, U, B = _plan(problem, X, U, f64)
+    X, U, B = plan_tensors(problem, X, U, device)
     K = torch.empty(B, problem.N, problem.nu, problem.nx, **f64)
     P0 = torch.empty(B, problem.nx, problem.nx, **f64)
     status = torch.empty(B, dtype=torch.int32, device=device)
-    check(lib().nlot_tvlqr_batch(C.byref(pc), C.byref(opt), _ptr(X), _ptr(U), _ptr(K), _ptr(P0), _ptr(status), B,
+    check(lib().nlot_tvlqr_batch(C.byref(pc), C.byref(opt), ptr(X), ptr(U), ptr(K), ptr(P0), ptr(status), B,
                                  stream_ptr()), "nlot_tvlqr_batch")
     return K, P0, status
 
@@ -64,36 +49,21 @@ def track_batch(problem: Problem, X, U, K=None, dx0=None, xg=None, obstacles=Non
     `obstacles`, xg, substeps, edge_points and the thresholds are rollout_batch's.  Returns rollout_batch's dict plus
     U_applied [B, N, nu] (fp64) and saturated [B] (int32: the knots at which the clamp acted); flags carry
     _abi.TRACK_* bits and ok = (flags == 0)."""
-    scene = problem.obstacles if obstacles is None else obstacles
     require_gpu()
-    if scene:
-        pc = problem.with_(sdf="analytic", obstacles=list(scene)).to_c()  # to_c() drops the scene of an mlp problem
-    else:
-        pc = problem.with_(sdf="mlp", obstacles=[]).to_c()  # n_obs == 0: no clearance
+    pc = scene_problem(problem, obstacles)  # without a scene: no clearance
     opt = _abi.track_options(substeps, edge_points, clamp, clearance_min, deviation_tol, goal_tol)
     f64 = dict(dtype=torch.float64, device=device)
-    X, U, B = _plan(problem, X, U, f64)
-    if K is not None:
-        K = torch.as_tensor(K, **f64).contiguous()
-        if K.shape != (B, problem.N, problem.nu, problem.nx):
-            raise ValueError(f"K must be [{B}, {problem.N}, {problem.nu}, {problem.nx}]")
-    if dx0 is not None:
-        dx0 = torch.as_tensor(dx0, **f64).contiguous()
-        if dx0.shape != (B, problem.nx):
-            raise ValueError(f"dx0 must be [{B}, {problem.nx}]")
-    if xg is not None:
-        xg = torch.as_tensor(xg, **f64).contiguous()
-        if xg.shape != (B, problem.nx):
-            raise ValueError(f"xg must be [{B}, {problem.nx}]")
+    X, U, B, K, dx0, xg = plan_tensors(problem, X, U, device, ("K", K, (problem.N, problem.nu, problem.nx)),
+                                       ("dx0", dx0, (problem.nx,)), ("xg", xg, (problem.nx,)))
     out = {k: torch.empty(B, **f64) for k in ("clearance", "deviation", "goal_error")}
     out["X_roll"] = torch.empty_like(X)
     out["U_applied"] = torch.empty_like(U)
     for k in ("where", "dev_where", "saturated", "flags"):
         out[k] = torch.empty(B, dtype=torch.int32, device=device)
-    check(lib().nlot_track_batch(C.byref(pc), C.byref(opt), _ptr(X), _ptr(U), _ptr(K), _ptr(dx0), _ptr(xg),
-                                 _ptr(out["X_roll"]), _ptr(out["U_applied"]), _ptr(out["clearance"]), _ptr(out["where"]),
-                                 _ptr(out["deviation"]), _ptr(out["dev_where"]), _ptr(out["goal_error"]),
-                                 _ptr(out["saturated"]), _ptr(out["flags"]), B, stream_ptr()), "nlot_track_batch")
+    check(lib().nlot_track_batch(C.byref(pc), C.byref(opt), ptr(X), ptr(U), ptr(K), ptr(dx0), ptr(xg),
+                                 ptr(out["X_roll"]), ptr(out["U_applied"]), ptr(out["clearance"]), ptr(out["where"]),
+                                 ptr(out["deviation"]), ptr(out["dev_where"]), ptr(out["goal_error"]),
+                                 ptr(out["saturated"]), ptr(out["flags"]), B, stream_ptr()), "nlot_track_batch")
     out["ok"] = out["flags"] == 0
     return {k: out[k] for k in ("X_roll", "U_applied", "clearance", "where", "deviation", "dev_where", "goal_error",
                                 "saturated", "flags", "ok")}
