@@ -13,6 +13,6 @@ grep -q "REGRESSION: 4e8db73" build/regress/nlot_solver.hip
 HIPFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-result -Wno-unused-function"
 /opt/rocm/bin/hipcc $HIPFLAGS -DNLOT_ONLY_DYN=5 -I. -c -o build/regress/nlot_solver.o build/regress/nlot_solver.hip
 /opt/rocm/bin/hipcc $HIPFLAGS -DNLOT_ONLY_DYN=5 -c -o build/regress/nlot_solve_api.o nlot_solve_api.hip
-/opt/rocm/bin/hipcc $HIPFLAGS -shared -o ../libnlot_regress.so build/nlot_capi.o build/nlot_mlp.o build/regress/nlot_solver.o \
+/opt/rocm/bin/hipcc $HIPFLAGS -shared -o ../libnlot_regress.so build/nlot_capi.o build/nlot_mlp*.o build/regress/nlot_solver.o \
     build/regress/nlot_solve_api.o build/nlot_rrt.o build/nlot_verify.o build/nlot_rollout.o
 echo built ../libnlot_regress.so

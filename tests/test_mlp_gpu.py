@@ -107,6 +107,17 @@ def test_mlp_relu_two_layer_vs_torch():
     assert float(hh.abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("hidden,n_hidden", [(64, 1), (128, 2), (64, 3), (128, 4)])
+def test_relu_f32_dispatch_cells_vs_torch(hidden, n_hidden):
+    """The ReLU dispatch cells no other test reaches: 64x1 and 128x2 on the LDS-resident f32 kernel, 64x3 and 128x4 on
+    the layer-streaming one, at 200 points (one full and one partial tile of either) with lam, against torch fp64.
+    The bars are those of the wider and deeper 256x4 stress net, so they bound these shallower fp32 chains too."""
+    from mlp_checks import check_vs_torch
+    from nlotrajectories_amd.nn import MlpWeights
+
+    check_vs_torch(MlpWeights.random_relu_mlp(hidden=hidden, n_hidden=n_hidden, seed=5), P=200, seed=2)
+
+
 @pytest.mark.parametrize("net", ["b6_trained", "relu_64x2", "relu_256x3"])
 def test_seq_arith_bitwise_oracle(net):
     """NLOT_MLP_ARITH_SEQ (include/nlot.h, ABI v15): every sum a sequential fp32 FMA chain in index order, the oracle's
