@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 19
+#define NLOT_ABI_VERSION 20
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -557,6 +557,68 @@ int32_t nlot_track_batch(const NlotProblem* prob, const NlotTrackOptions* opt, c
                          const double* K, const double* dx0, const double* xg, double* X_roll, double* U_applied,
                          double* clearance, int32_t* where, double* deviation, int32_t* dev_where, double* goal_error,
                          int32_t* saturated, int32_t* flags, int64_t B, void* stream);
+
+/* ---- training the learned SDF on the device (ABI v20) --------------------------------------------
+ * The reference trains a network per l4casadi-mode run (core/sdf/l4casadi.py:125-228: Adam on MSE + surface loss +
+ * eikonal loss, batches of 256).  nlot_sdf_train_steps runs consecutive optimiser steps of that loop in one kernel
+ * launch, one workgroup per network, for the net every shipped config describes: the ReLU MLP 2-128-128-1
+ * (DESIGN.md section 14).  All arithmetic is fp32, equal to torch's fp32 up to summation order.
+ *
+ * One step, on the batch's n_b <= 256 rows (x_i, y_i), f = the net, g_i = df/dx at x_i, S = {i : |y_i| < surface_eps}:
+ *   loss = mean (f_i - y_i)^2 + surface_weight * mean_{i in S} f_i^2 + eikonal_weight * mean (|g_i| - 1)^2
+ * (the surface term is absent when S is empty or surface_weight == 0; g's dependence on the weights is
+ * differentiated with the ReLU masks held constant, and |g| = 0 contributes no gradient, both as torch's autograd),
+ * then torch.optim.Adam's update with no weight decay:
+ *   m <- m + (1 - beta1) (grad - m),  v <- beta2 v + (1 - beta2) grad^2,
+ *   p <- p - lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + adam_eps)
+ * State of one network, nlot_sdf_train_state_floats() = 3 * 17025 + 1 fp32 words: the parameters in torch's
+ * parameters() order (W1 [128][2], b1 [128], W2 [128][128], b2 [128], w3 [128], b3), then m and v in the same order,
+ * then the step count t as an int32 bit pattern.  An all-zero m, v, t is a fresh optimiser. */
+typedef struct NlotSdfTrainOptions {
+    int32_t hidden;         /* 128 */
+    int32_t n_hidden;       /* hidden x hidden layers: 1 */
+    int32_t batch;          /* 256 */
+    int32_t pad_;
+    double lr;              /* 1e-3 */
+    double beta1, beta2;    /* 0.9, 0.999 */
+    double adam_eps;        /* 1e-8 */
+    double surface_weight;  /* 0 */
+    double surface_eps;     /* 1e-2 */
+    double eikonal_weight;  /* 0 */
+} NlotSdfTrainOptions;
+/* Fill `opt` with the defaults documented above. */
+void nlot_sdf_train_default_options(NlotSdfTrainOptions* opt);
+/* fp32 words of one network's state; 0 for a null or unsupported opt. */
+int64_t nlot_sdf_train_state_floats(const NlotSdfTrainOptions* opt);
+/* Train M independent networks, network m on its own data, order and state.
+ *   state  [M][state_floats] fp32 device, read at entry and written at exit, so that an epoch may be one call or
+ *          several
+ *   pts    [M][n][2], target [M][n] fp32 device: the rows
+ *   order  [M][n_rows] int32 device: the sequence of row indices (an epoch's permutation).  The call runs the
+ *          batches that cover positions first_row .. n_rows - 1 of it: step s takes positions first_row + 256 s ..
+ *          first_row + 256 s + 255, the last step the n_rows - first_row - 256 s that remain, so
+ *          n_steps = ceil((n_rows - first_row) / 256).  An index outside [0, n) is clamped into it.  Network m's
+ *          sequence starts at order + m * n_rows: a caller who splits an epoch of several networks over calls by
+ *          moving n_rows must lay `order` out anew for each call (with M = 1 the same array serves every call).
+ *   step_loss [M][n_steps] fp32 device: each step's loss before its update (an epoch's loss is
+ *          sum step_loss * n_b / n_rows)
+ *   grad_last [M][17025] fp32 device or NULL: the last step's gradient, in the parameters' order
+ * A network's outputs depend on its own inputs only and every sum has a fixed order: they are bitwise the same
+ * whatever M is, wherever in the call the network sits and however the steps are split over calls.
+ * Asynchronous on `stream`; no workspace, no global state, no synchronisation between workgroups.
+ * NLOT_ERR_INVALID before any device call for: a null pointer other than grad_last; hidden != 128, n_hidden != 1 or
+ * batch != 256; lr not > 0, a beta outside [0, 1), a negative adam_eps or weight, surface_eps not > 0, or any of
+ * them not finite; M outside 1 .. 65535; n or n_rows outside 1 .. 2^30; first_row negative, not below n_rows or not a
+ * multiple of 256. */
+int32_t nlot_sdf_train_steps(const NlotSdfTrainOptions* opt, float* state, const float* pts, const float* target,
+                             const int32_t* order, int64_t n, int64_t first_row, int64_t n_rows, float* step_loss,
+                             float* grad_last, int64_t M, void* stream);
+/* The validation loss of the trainer per batch: batch_loss [M][ceil(n / 256)] fp32 device, entry b of network m being
+ * mean (f_i - y_i)^2 + surface_weight * mean_{i in S} f_i^2 over rows 256 b .. min(256 b + 255, n - 1) of pts [M][n][2]
+ * and target [M][n] in their stored order (S taken within the batch, the term absent when it is empty).  Only the
+ * parameters of `state` are read.  Errors as nlot_sdf_train_steps' for opt, the pointers, M and n. */
+int32_t nlot_sdf_batch_loss(const NlotSdfTrainOptions* opt, const float* state, const float* pts, const float* target,
+                            int64_t n, float* batch_loss, int64_t M, void* stream);
 
 casadi_int_t nn_sdf_n_in(void);
 casadi_int_t nn_sdf_n_out(void);

@@ -223,3 +223,23 @@ class NlotSdfMetrics(C.Structure):
 def sdf_metrics_options(threshold=0.0, eps=1e-2) -> NlotSdfMetricsOptions:
     """The defaults of nlot_default_sdf_metrics_options (core/metrics.py's threshold and eps)."""
     return NlotSdfMetricsOptions(threshold=float(threshold), eps=float(eps))
+
+
+# nlot_sdf_train_steps / nlot_sdf_batch_loss (include/nlot.h, ABI v20)
+SDF_TRAIN_PARAMS = 17025  # the ReLU MLP 2-128-128-1 in torch's parameters() order
+
+
+class NlotSdfTrainOptions(C.Structure):
+    """include/nlot.h NlotSdfTrainOptions."""
+    _fields_ = [("hidden", C.c_int32), ("n_hidden", C.c_int32), ("batch", C.c_int32), ("pad_", C.c_int32),
+                ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_eps", C.c_double),
+                ("surface_weight", C.c_double), ("surface_eps", C.c_double), ("eikonal_weight", C.c_double)]
+
+
+def sdf_train_options(lr=1e-3, surface_weight=0.0, surface_eps=1e-2, eikonal_weight=0.0, beta1=0.9, beta2=0.999,
+                      adam_eps=1e-8, hidden=128, n_hidden=1, batch=256) -> NlotSdfTrainOptions:
+    """The defaults of nlot_sdf_train_default_options (torch.optim.Adam's, both extra loss terms off)."""
+    return NlotSdfTrainOptions(hidden=int(hidden), n_hidden=int(n_hidden), batch=int(batch), pad_=0, lr=float(lr),
+                               beta1=float(beta1), beta2=float(beta2), adam_eps=float(adam_eps),
+                               surface_weight=float(surface_weight), surface_eps=float(surface_eps),
+                               eikonal_weight=float(eikonal_weight))

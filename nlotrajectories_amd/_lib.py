@@ -27,6 +27,7 @@ EXPORTED = [
     "nlot_default_verify_options", "nlot_verify_batch", "nlot_default_rollout_options", "nlot_rollout_batch",
     "nlot_scene_sdf_eval", "nlot_default_sdf_metrics_options", "nlot_sdf_metrics",
     "nlot_default_tvlqr_options", "nlot_tvlqr_batch", "nlot_default_track_options", "nlot_track_batch",
+    "nlot_sdf_train_default_options", "nlot_sdf_train_state_floats", "nlot_sdf_train_steps", "nlot_sdf_batch_loss",
 ]
 
 
@@ -106,9 +107,18 @@ def lib():
     L.nlot_track_batch.argtypes = [C.POINTER(_abi.NlotProblem), C.POINTER(_abi.NlotTrackOptions), vp, vp, vp, vp, vp,
                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp]
     L.nlot_track_batch.restype = C.c_int32
+    L.nlot_sdf_train_default_options.argtypes = [C.POINTER(_abi.NlotSdfTrainOptions)]
+    L.nlot_sdf_train_default_options.restype = None
+    L.nlot_sdf_train_state_floats.argtypes = [C.POINTER(_abi.NlotSdfTrainOptions)]
+    L.nlot_sdf_train_state_floats.restype = C.c_int64
+    L.nlot_sdf_train_steps.argtypes = [C.POINTER(_abi.NlotSdfTrainOptions), vp, vp, vp, vp, C.c_int64, C.c_int64,
+                                       C.c_int64, vp, vp, C.c_int64, vp]
+    L.nlot_sdf_train_steps.restype = C.c_int32
+    L.nlot_sdf_batch_loss.argtypes = [C.POINTER(_abi.NlotSdfTrainOptions), vp, vp, vp, C.c_int64, vp, C.c_int64, vp]
+    L.nlot_sdf_batch_loss.restype = C.c_int32
     L.nlot_casadi_bind.argtypes = [vp]
     L.nlot_casadi_bind.restype = C.c_int32
-    if L.nlot_abi_version() != 19:
+    if L.nlot_abi_version() != 20:
         raise NlotError("libnlot.so ABI version mismatch")
     _lib = L
     return L

@@ -121,6 +121,7 @@ def _print_track(prob, r, xg, substeps, edge_points, q, rw, qf):
 def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="results", verbose=True,
                   options=None, metrics=True, verify=False, verify_sub=8, verify_edge_points=3, rollout=False,
                   rollout_substeps=8, rollout_edge_points=3, metrics_device="host", train_sdf_device="host",
+                  train_backend="torch",
                   track=False, track_substeps=8, track_edge_points=3, track_q=1.0, track_r=1.0, track_qf=1.0):
     """Returns (X_opt [nx, N+1], U_opt [nu, N], status str) like RunBenchmark.run (runner.py:148-153).
     verify=True also prints the trajectory's exact clearance, dynamics defect and collision verdict; rollout=True the
@@ -140,7 +141,7 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
         if weights == "train":  # run_benchmark.py:84-95
             from .trainer import train_for_config
 
-            model, _ = train_for_config(cfg, verbose=verbose, sdf_device=train_sdf_device)
+            model, _ = train_for_config(cfg, verbose=verbose, sdf_device=train_sdf_device, backend=train_backend)
             w = MlpWeights.from_module(model)
         else:
             w = MlpWeights.artefact() if weights == "artefact" else MlpWeights.load(weights)
@@ -263,6 +264,9 @@ def _parser():
     ap.add_argument("--track-qf", type=float, nargs="+", default=[1.0], help="--track: state weight at the last knot")
     ap.add_argument("--metrics-device", choices=["host", "gpu"], default="host",
                     help="where the SDF-quality metrics are computed: numpy (scene.py) or the GPU (scene_gpu.py)")
+    ap.add_argument("--train-backend", choices=["torch", "hip"], default="torch",
+                    help="--weights train: the PyTorch loop, or the persistent HIP training kernel (the ReLU net "
+                         "2-128-128-1 in batches of 256 only)")
     ap.add_argument("--train-sdf-device", choices=["host", "gpu"], default="host",
                     help="--weights train: where the training targets (the scene's exact SDF) are evaluated")
     return ap
@@ -278,7 +282,8 @@ def main(argv=None):
     run_benchmark(Path(a.config), initializer=a.initializer, weights=a.weights, results_dir=a.results, verify=a.verify,
                   verify_sub=a.verify_sub, verify_edge_points=a.verify_edge_points, rollout=a.rollout,
                   rollout_substeps=a.rollout_substeps, rollout_edge_points=a.rollout_edge_points,
-                  metrics_device=a.metrics_device, train_sdf_device=a.train_sdf_device, track=a.track,
+                  metrics_device=a.metrics_device, train_sdf_device=a.train_sdf_device,
+                  train_backend=a.train_backend, track=a.track,
                   track_substeps=a.track_substeps, track_edge_points=a.track_edge_points, track_q=_weight(a.track_q),
                   track_r=_weight(a.track_r), track_qf=_weight(a.track_qf))
 

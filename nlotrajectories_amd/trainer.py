@@ -15,6 +15,10 @@ with early stopping on a 10 % validation split.  Differences, all deliberate:
   the samples stays at the default 0.3 — reproduced, not fixed.
 
 The product consumes the trained module through `MlpWeights.from_module` (ReLU MLP / FourierMLP kernels).
+
+`backend="hip"` runs the batch loop and the validation loop in the library's training kernels
+(nlot_sdf_train_steps, nlot_sdf_batch_loss) for the shipped ReLU net 2-128-128-1; data, split,
+per-epoch permutation, early stopping and best-state restore are the code the torch backend runs.
 """
 from __future__ import annotations
 
@@ -84,13 +88,18 @@ class NNObstacleTrainer:
     def __init__(self, obstacles, model: nn.Module, device=None, epochs: int = 100, eikonal_weight: float = 0,
                  surface_loss_weight: float = 0, n_samples: int = 200000, boundary_fraction: float = 0.3,
                  random: bool = True, batch_size: int = 256, lr: float = 1e-3, seed: int = 0, verbose: bool = True,
-                 sdf_device: str = "host"):
+                 sdf_device: str = "host", backend: str = "torch"):
         if sdf_device not in ("host", "gpu"):
             raise ValueError(f"sdf_device must be 'host' or 'gpu', not {sdf_device!r}")
+        if backend not in ("torch", "hip"):
+            raise ValueError(f"backend must be 'torch' or 'hip', not {backend!r}")
+        if backend == "hip":
+            _check_hip_backend(model, batch_size, device)
+        self.backend = backend
         self.obstacles = obstacles
         self.sdf_device = sdf_device
         if device is None:
-            device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+            device = torch.device("cuda" if backend == "hip" or torch.cuda.is_available() else "cpu")
         self.device = torch.device(device)
         self.seed = seed
         self.gen = torch.Generator().manual_seed(seed)
@@ -145,29 +154,33 @@ class NNObstacleTrainer:
         X, Y = X[idx].to(self.device), Y[idx].to(self.device)
         n_val = int(0.1 * len(X))
         X_val, Y_val, X_tr, Y_tr = X[:n_val], Y[:n_val], X[n_val:], Y[n_val:]
-        opt = torch.optim.Adam(self.model.parameters(), lr=self.lr)
+        hip = _HipLoops(self, X_tr, Y_tr, X_val, Y_val, surface_loss_eps) if self.backend == "hip" else None
+        opt = torch.optim.Adam(self.model.parameters(), lr=self.lr) if hip is None else None
         loss_fn = nn.MSELoss()
         best, best_state, bad = float("inf"), copy.deepcopy(self.model.state_dict()), 0
         bs = self.batch_size
         self.model.train()
         for ep in range(self.epochs):
             perm = torch.randperm(len(X_tr), generator=self.gen).to(self.device)
-            total = torch.zeros((), device=self.device)
-            for i in range(0, len(X_tr), bs):
-                j = perm[i:i + bs]
-                xb, yb = X_tr[j], Y_tr[j]
-                loss = self._loss(xb, yb, loss_fn, surface_loss_eps, True)
-                opt.zero_grad()
-                loss.backward()
-                opt.step()
-                total += loss.detach() * len(j)
-            self.model.eval()
-            val = torch.zeros((), device=self.device)
-            with torch.no_grad():
-                for i in range(0, n_val, bs):
-                    xb, yb = X_val[i:i + bs], Y_val[i:i + bs]
-                    val += self._loss(xb, yb, loss_fn, surface_loss_eps, False) * len(xb)
-            self.model.train()
+            if hip is not None:
+                total, val = hip.epoch(perm)
+            else:
+                total = torch.zeros((), device=self.device)
+                for i in range(0, len(X_tr), bs):
+                    j = perm[i:i + bs]
+                    xb, yb = X_tr[j], Y_tr[j]
+                    loss = self._loss(xb, yb, loss_fn, surface_loss_eps, True)
+                    opt.zero_grad()
+                    loss.backward()
+                    opt.step()
+                    total += loss.detach() * len(j)
+                self.model.eval()
+                val = torch.zeros((), device=self.device)
+                with torch.no_grad():
+                    for i in range(0, n_val, bs):
+                        xb, yb = X_val[i:i + bs], Y_val[i:i + bs]
+                        val += self._loss(xb, yb, loss_fn, surface_loss_eps, False) * len(xb)
+                self.model.train()
             tr_loss, val_loss = float(total) / len(X_tr), float(val) / max(n_val, 1)
             self.history.append((tr_loss, val_loss))
             if self.verbose:
@@ -186,6 +199,76 @@ class NNObstacleTrainer:
         return self.model
 
 
+def _check_hip_backend(model, batch_size, device):
+    """backend="hip" trains one architecture: the ReLU MultiLayerPerceptron(2, 128, 1, 2) in batches of 256, with
+    everything on a GPU (the kernels take device pointers)."""
+    from .nn import MultiLayerPerceptron
+
+    ok = (isinstance(model, MultiLayerPerceptron) and model.activation == "ReLU" and len(model.hidden_layers) == 1
+          and tuple(model.input_layer.weight.shape) == (128, 2) and tuple(model.output_layer.weight.shape) == (1, 128))
+    if not ok:
+        raise ValueError('backend="hip" trains the ReLU MultiLayerPerceptron(2, 128, 1, 2) only; use backend="torch" '
+                         "for any other network")
+    if batch_size != 256:
+        raise ValueError(f'backend="hip" needs batch_size=256, not {batch_size}; use backend="torch" for other sizes')
+    if device is not None and torch.device(device).type != "cuda":
+        raise ValueError(f'backend="hip" trains on a GPU, not on device {str(device)!r}; use backend="torch" there')
+
+
+class _HipLoops:
+    """The batch loop and the validation loop of NNObstacleTrainer.train on the library's kernels.  The state block
+    (parameters, Adam moments, step count; include/nlot.h) lives on the device for the whole training."""
+
+    STEPS_PER_LAUNCH = 2048
+
+    def __init__(self, tr, X_tr, Y_tr, X_val, Y_val, surface_loss_eps):
+        import ctypes as C
+
+        from . import _abi, _lib
+
+        _lib.require_gpu()
+        self.C, self.L, self.lib = C, _lib, _lib.lib()
+        self.tr = tr
+        self.opt = _abi.sdf_train_options(lr=tr.lr, surface_weight=tr.surface_loss_weight, surface_eps=surface_loss_eps,
+                                          eikonal_weight=tr.eikonal_weight)
+        self.X_tr, self.Y_tr = X_tr.contiguous(), Y_tr.reshape(-1).contiguous()
+        self.X_val, self.Y_val = X_val.contiguous(), Y_val.reshape(-1).contiguous()
+        assert all(t.is_cuda and t.dtype == torch.float32 for t in (self.X_tr, self.Y_tr, self.X_val, self.Y_val))
+        self.state = torch.zeros(self.lib.nlot_sdf_train_state_floats(C.byref(self.opt)), device=tr.device)
+        self.n_par = _abi.SDF_TRAIN_PARAMS
+        self.state[:self.n_par] = torch.nn.utils.parameters_to_vector(tr.model.parameters()).detach().float()
+
+    def epoch(self, perm):
+        """One epoch over the permutation `perm`, then the validation pass: (sum of loss x rows over the training
+        batches, the same over the validation batches) as device scalars; the model's parameters are updated."""
+        C, L, bs = self.C, self.L, 256
+        n_tr, n_val = len(self.X_tr), len(self.X_val)
+        order = perm.to(torch.int32).contiguous()
+        n_steps = (n_tr + bs - 1) // bs
+        losses = torch.empty(n_steps, device=order.device)
+        for s0 in range(0, n_steps, self.STEPS_PER_LAUNCH):
+            end = min(n_tr, (s0 + self.STEPS_PER_LAUNCH) * bs)
+            L.check(self.lib.nlot_sdf_train_steps(C.byref(self.opt), L.ptr(self.state), L.ptr(self.X_tr),
+                                                  L.ptr(self.Y_tr), L.ptr(order), n_tr, s0 * bs, end, L.ptr(losses[s0:]),
+                                                  None, 1, L.stream_ptr()), "nlot_sdf_train_steps")
+        rows = torch.full((n_steps,), float(bs), device=order.device)
+        rows[-1] = n_tr - (n_steps - 1) * bs
+        total = (losses * rows).sum()
+        val = torch.zeros((), device=order.device)
+        if n_val > 0:
+            nb = (n_val + bs - 1) // bs
+            bl = torch.empty(nb, device=order.device)
+            L.check(self.lib.nlot_sdf_batch_loss(C.byref(self.opt), L.ptr(self.state), L.ptr(self.X_val),
+                                                 L.ptr(self.Y_val), n_val, L.ptr(bl), 1, L.stream_ptr()),
+                    "nlot_sdf_batch_loss")
+            rows = torch.full((nb,), float(bs), device=order.device)
+            rows[-1] = n_val - (nb - 1) * bs
+            val = (bl * rows).sum()
+        with torch.no_grad():
+            torch.nn.utils.vector_to_parameters(self.state[:self.n_par].clone(), self.tr.model.parameters())
+        return total, val
+
+
 def model_from_config(mc):
     """scripts/run_benchmark.py:55-83: the network a YAML's `model:` section describes (mlp / fourier / siren)."""
     from .nn import SIREN, FourierMLP, MultiLayerPerceptron
@@ -200,12 +283,12 @@ def model_from_config(mc):
     raise ValueError(f"Unsupported model type: {mc.type}")
 
 
-def train_for_config(cfg, seed=0, device=None, epochs=100, verbose=True, sdf_device="host"):
+def train_for_config(cfg, seed=0, device=None, epochs=100, verbose=True, sdf_device="host", backend="torch"):
     """run_benchmark.py:84-95: train the config's network on its scene over (-0.5, 1.5)^2."""
     mc = cfg.model
     model = model_from_config(mc)
     tr = NNObstacleTrainer(cfg.obstacle_dicts(), model, device=device, epochs=epochs, n_samples=mc.n_samples,
                            boundary_fraction=mc.boundary_fraction, eikonal_weight=mc.eikonal_loss_weight,
                            surface_loss_weight=mc.surface_loss_weight, seed=seed, verbose=verbose,
-                           sdf_device=sdf_device)
+                           sdf_device=sdf_device, backend=backend)
     return tr.train((-0.5, 1.5), (-0.5, 1.5)), tr
