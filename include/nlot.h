@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 20
+#define NLOT_ABI_VERSION 21
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -217,10 +217,15 @@ NlotMlp* nlot_mlp_create(const NlotMlpDesc* desc);
  *   NLOT_MLP_ARITH_F32         v_mfma_f32 products (the reference's fp32 net, gen/nn_sdf.cpp, at the f32 peak)
  *   NLOT_MLP_ARITH_SEQ         (ABI v15; ReLU nets) every sum a sequential fp32 FMA chain in index order, one thread per
  *                              point: a fixed, documented summation order (the test oracle's), for bitwise-reproducible
- *                              comparisons; not a throughput path */
+ *                              comparisons; not a throughput path
+ *   NLOT_MLP_ARITH_HDUAL_MFMA  (ABI v21; smooth activations: tanh, sigmoid, leaky ReLU, sine) value, gradient and Hessian
+ *                              carried forward as hyper-duals through v_mfma_f32 products, every HxH layer resident in
+ *                              LDS: hidden width 128 with 1-2 HxH layers or 64 with 1-4.  Opt-in: a smooth net created
+ *                              with any other value takes the scalar-FMA kernel.  Refused for ReLU nets */
 #define NLOT_MLP_ARITH_SPLIT_BF16 0
 #define NLOT_MLP_ARITH_F32 1
 #define NLOT_MLP_ARITH_SEQ 2
+#define NLOT_MLP_ARITH_HDUAL_MFMA 3
 NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* desc, int32_t arith);
 void nlot_mlp_destroy(NlotMlp* mlp);
 

@@ -121,12 +121,13 @@ def _print_track(prob, r, xg, substeps, edge_points, q, rw, qf):
 def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="results", verbose=True,
                   options=None, metrics=True, verify=False, verify_sub=8, verify_edge_points=3, rollout=False,
                   rollout_substeps=8, rollout_edge_points=3, metrics_device="host", train_sdf_device="host",
-                  train_backend="torch",
+                  train_backend="torch", mlp_arith="split_bf16",
                   track=False, track_substeps=8, track_edge_points=3, track_q=1.0, track_r=1.0, track_qf=1.0):
     """Returns (X_opt [nx, N+1], U_opt [nu, N], status str) like RunBenchmark.run (runner.py:148-153).
     verify=True also prints the trajectory's exact clearance, dynamics defect and collision verdict; rollout=True the
     clearance, deviation from the plan and goal error of the controls rolled through the continuous dynamics;
-    track=True the same and the saturated knots of the plan tracked with its TVLQR gains."""
+    track=True the same and the saturated knots of the plan tracked with its TVLQR gains.  mlp_arith: the learned SDF's
+    arithmetic (DeviceMlp.ARITH; "hdual_mfma" puts a smooth-activation net on the MFMA hyper-dual kernel)."""
     config_path = Path(config_path)
     cfg = Config.load(config_path)
     if cfg.solver.type != "ipopt":
@@ -145,7 +146,7 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
             w = MlpWeights.from_module(model)
         else:
             w = MlpWeights.artefact() if weights == "artefact" else MlpWeights.load(weights)
-        mlp = DeviceMlp(w)
+        mlp = DeviceMlp(w, mlp_arith)
     x0 = np.asarray(cfg.body.start_state, float)[None]
     xg = np.asarray(cfg.body.goal_state, float)[None]
     if x0.shape[1] != prob.nx or xg.shape[1] != prob.nx:
@@ -267,6 +268,9 @@ def _parser():
     ap.add_argument("--train-backend", choices=["torch", "hip"], default="torch",
                     help="--weights train: the PyTorch loop, or the persistent HIP training kernel (the ReLU net "
                          "2-128-128-1 in batches of 256 only)")
+    ap.add_argument("--mlp-arith", choices=["split_bf16", "f32", "seq", "hdual_mfma"], default="split_bf16",
+                    help="the learned SDF's kernel arithmetic (DeviceMlp); hdual_mfma: the MFMA hyper-dual kernel for "
+                         "smooth activations (hidden width 128 with 1-2 HxH layers, 64 with 1-4)")
     ap.add_argument("--train-sdf-device", choices=["host", "gpu"], default="host",
                     help="--weights train: where the training targets (the scene's exact SDF) are evaluated")
     return ap
@@ -283,7 +287,7 @@ def main(argv=None):
                   verify_sub=a.verify_sub, verify_edge_points=a.verify_edge_points, rollout=a.rollout,
                   rollout_substeps=a.rollout_substeps, rollout_edge_points=a.rollout_edge_points,
                   metrics_device=a.metrics_device, train_sdf_device=a.train_sdf_device,
-                  train_backend=a.train_backend, track=a.track,
+                  train_backend=a.train_backend, mlp_arith=a.mlp_arith, track=a.track,
                   track_substeps=a.track_substeps, track_edge_points=a.track_edge_points, track_q=_weight(a.track_q),
                   track_r=_weight(a.track_r), track_qf=_weight(a.track_qf))
 

@@ -90,7 +90,7 @@ struct MlpDev {
     int in_kind;     // NLOT_MLP_IN_*
     int H;           // hidden width
     int n_hidden;    // HxH layers
-    int act;         // NLOT_ACT_* (ReLU: the MFMA kernels; smooth activations: mlp_smooth)
+    int act;         // NLOT_ACT_* (ReLU: the MFMA kernels; smooth activations: mlp_smooth, or mlp_hdual by arith)
     float scale;     // fourier scale; omega_0 for NLOT_ACT_SINE
     float b_out;
     const float* A;     // [2][H]

@@ -1,5 +1,5 @@
-// What the learned-SDF MLP kernel families share (internal): nlot_mlp_f32.hip, nlot_mlp_bf16.hip, nlot_mlp_stream.hip
-// and nlot_mlp_ref.hip hold one family each behind the launcher declared here; nlot_mlp.hip chooses among them.
+// What the learned-SDF MLP kernel families share (internal): nlot_mlp_f32.hip, nlot_mlp_bf16.hip, nlot_mlp_stream.hip,
+// nlot_mlp_hdual.hip and nlot_mlp_ref.hip hold one family each behind the launcher declared here; nlot_mlp.hip chooses among them.
 #pragma once
 #include "nlot_internal.h"
 
@@ -94,6 +94,33 @@ __device__ __forceinline__ void input_contract(float ax, float ay, float z, floa
     hyy = fmaf(ay * ay, c2, hyy);
 }
 
+// s(z), s'(z), s''(z) of the activation: mlp_smooth and mlp_hdual evaluate them by these expressions
+__device__ __forceinline__ void act3(int act, float omega, float z, float& s, float& d1, float& d2) {
+    if (act == NLOT_ACT_TANH) {
+        s = tanhf(z);
+        d1 = 1.f - s * s;
+        d2 = -2.f * s * d1;
+    } else if (act == NLOT_ACT_SIGMOID) {
+        s = 1.f / (1.f + expf(-z));
+        d1 = s * (1.f - s);
+        d2 = d1 * (1.f - 2.f * s);
+    } else if (act == NLOT_ACT_LEAKY_RELU) {
+        s = z > 0.f ? z : 0.01f * z;
+        d1 = z > 0.f ? 1.f : 0.01f;
+        d2 = 0.f;
+    } else if (act == NLOT_ACT_SINE) {
+        const float u = omega * z;  // torch: sin(omega_0 * linear(x)), the product rounded first
+        s = sinf(u);
+        const float c = cosf(u);
+        d1 = omega * c;
+        d2 = -omega * omega * s;
+    } else {  // ReLU
+        s = z > 0.f ? z : 0.f;
+        d1 = z > 0.f ? 1.f : 0.f;
+        d2 = 0.f;
+    }
+}
+
 // blocks of a persistent launch: one per tile of points_per_tile points, at least 1 and at most cap
 inline int persistent_grid(int64_t points, int points_per_tile, int64_t cap) {
     const int64_t tiles = (points + points_per_tile - 1) / points_per_tile;
@@ -111,8 +138,20 @@ inline int dispatch_width(int H, F&& f) {
     return NLOT_ERR_INVALID;
 }
 
+// NLOT_MLP_ARITH_HDUAL_MFMA keeps every HxH layer in LDS (nlot_mlp_hdual.hip): the layers that fit beside 160 KB
+inline int hdual_max_layers(int H) { return H == 128 ? 2 : H == 64 ? 4 : 0; }
+// null when mlp_hdual serves the net, else why not (nlot_mlp_create_ex refuses with it before any device call)
+inline const char* hdual_refusal(int act, int H, int n_hidden) {
+    if (act == NLOT_ACT_RELU || n_hidden < 1 || n_hidden > hdual_max_layers(H))
+        return "NLOT_MLP_ARITH_HDUAL_MFMA serves smooth activations (tanh, sigmoid, leaky ReLU, sine) with hidden width "
+               "128 and 1-2 HxH layers or hidden width 64 and 1-4; ReLU nets take the reverse-sweep arithmetics, other "
+               "smooth shapes NLOT_MLP_ARITH_F32 (mlp_smooth)";
+    return nullptr;
+}
+
 // One launcher per family, arguments as launch_mlp_strided's, which has checked w.n_hidden for the family: f32 takes
-// H <= 128 with 1 or 2 HxH layers, bf16 H = 128 with one HxH layer and w.Wp, the others every width
+// H <= 128 with 1 or 2 HxH layers, bf16 H = 128 with one HxH layer and w.Wp, hdual what hdual_refusal passes, the
+// others every width
 int launch_mlp_f32(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                    const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_bf16(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
@@ -121,6 +160,8 @@ int launch_mlp_stream(const MlpDev& w, const float* pts, int64_t n, const int* n
                       const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_smooth(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                       const float* lam, const MlpOut& out, bool full, hipStream_t stream);
+int launch_mlp_hdual(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
+                     const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_seq(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                    const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 

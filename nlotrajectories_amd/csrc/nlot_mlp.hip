@@ -37,6 +37,8 @@ int launch_mlp_strided(const MlpDev& w, const float* pts, int64_t n, const int* 
     if (n <= 0) return NLOT_OK;
     if (w.arith == NLOT_MLP_ARITH_SEQ)  // ReLU nets only (nlot_mlp_create_ex checks)
         return launch_mlp_seq(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
+    if (w.arith == NLOT_MLP_ARITH_HDUAL_MFMA)  // smooth nets whose layers fit in LDS (nlot_mlp_create_ex checks)
+        return launch_mlp_hdual(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
     if (w.act != NLOT_ACT_RELU) {  // smooth activations: forward hyper-duals (the ReLU masks / reuse do not apply)
         if (w.n_hidden < 0 || w.n_hidden > kMaxStreamLayers) {
             set_error("MLP kernel: 0 to 4 hidden HxH layers are supported for smooth activations");
@@ -68,8 +70,10 @@ extern "C" NlotMlp* nlot_mlp_create(const NlotMlpDesc* d) { return nlot_mlp_crea
 
 extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
     using namespace nlot;
-    if (arith != NLOT_MLP_ARITH_SPLIT_BF16 && arith != NLOT_MLP_ARITH_F32 && arith != NLOT_MLP_ARITH_SEQ) {
-        set_error("nlot_mlp_create_ex: arith must be NLOT_MLP_ARITH_SPLIT_BF16, NLOT_MLP_ARITH_F32 or NLOT_MLP_ARITH_SEQ");
+    if (arith != NLOT_MLP_ARITH_SPLIT_BF16 && arith != NLOT_MLP_ARITH_F32 && arith != NLOT_MLP_ARITH_SEQ &&
+        arith != NLOT_MLP_ARITH_HDUAL_MFMA) {
+        set_error("nlot_mlp_create_ex: arith must be NLOT_MLP_ARITH_SPLIT_BF16, NLOT_MLP_ARITH_F32, NLOT_MLP_ARITH_SEQ or "
+                  "NLOT_MLP_ARITH_HDUAL_MFMA");
         return nullptr;
     }
     if (arith == NLOT_MLP_ARITH_SEQ && d && d->act != NLOT_ACT_RELU) {
@@ -92,11 +96,17 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
                   "activations; DESIGN.md §7)");
         return nullptr;
     }
+    if (arith == NLOT_MLP_ARITH_HDUAL_MFMA) {
+        if (const char* why = hdual_refusal(d->act, d->hidden, d->n_hidden)) {
+            set_error(std::string("nlot_mlp_create_ex: ") + why);
+            return nullptr;
+        }
+    }
     const int H = d->hidden, L = d->n_hidden;
     const size_t nA = 2 * H, nb0 = H, nW = (size_t)L * H * H, nb = (size_t)L * H, nw = H;
     const bool split = arith == NLOT_MLP_ARITH_SPLIT_BF16;
     const size_t nWp = split ? (size_t)3 * H * H / 2 : 0;  // bf16 planes of layer 0, in float units
-    const size_t nWt = smooth ? nW : 0;        // transposed HxH layers (mlp_smooth)
+    const size_t nWt = smooth && arith != NLOT_MLP_ARITH_HDUAL_MFMA ? nW : 0;  // transposed HxH layers (mlp_smooth)
     const size_t total = nA + nb0 + nW + nb + nw + nWp + nWt + 4;
     float* blk = nullptr;
     if (hipMalloc(&blk, total * sizeof(float)) != hipSuccess) {
@@ -153,7 +163,7 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
         m->dev.Wp = put(reinterpret_cast<const float*>(planes.data()), nWp);
     }
     m->dev.Wt = nullptr;
-    if (smooth && L > 0) {  // [l][in][out] for mlp_smooth's coalesced rows
+    if (nWt) {  // [l][in][out] for mlp_smooth's coalesced rows
         std::vector<float> wt(nW);
         for (int l = 0; l < L; ++l)
             for (int o = 0; o < H; ++o)

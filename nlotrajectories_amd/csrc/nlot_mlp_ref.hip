@@ -18,33 +18,6 @@ namespace nlot {
 // ---------------------------------------------------------------------------------------------
 constexpr int kSmoothPB = 8;
 
-// s(z), s'(z), s''(z) of the activation
-__device__ __forceinline__ void act3(int act, float omega, float z, float& s, float& d1, float& d2) {
-    if (act == NLOT_ACT_TANH) {
-        s = tanhf(z);
-        d1 = 1.f - s * s;
-        d2 = -2.f * s * d1;
-    } else if (act == NLOT_ACT_SIGMOID) {
-        s = 1.f / (1.f + expf(-z));
-        d1 = s * (1.f - s);
-        d2 = d1 * (1.f - 2.f * s);
-    } else if (act == NLOT_ACT_LEAKY_RELU) {
-        s = z > 0.f ? z : 0.01f * z;
-        d1 = z > 0.f ? 1.f : 0.01f;
-        d2 = 0.f;
-    } else if (act == NLOT_ACT_SINE) {
-        const float u = omega * z;  // torch: sin(omega_0 * linear(x)), the product rounded first
-        s = sinf(u);
-        const float c = cosf(u);
-        d1 = omega * c;
-        d2 = -omega * omega * s;
-    } else {  // ReLU
-        s = z > 0.f ? z : 0.f;
-        d1 = z > 0.f ? 1.f : 0.f;
-        d2 = 0.f;
-    }
-}
-
 template <int H, bool FULL>
 __global__ __launch_bounds__(256) void mlp_smooth(MlpDev w, const float* __restrict__ pts, int64_t cnt_host,
                                                   const int* __restrict__ cnt_dev, int P_per, int64_t ld,

@@ -15,9 +15,12 @@ class DeviceMlp:
     """Device-resident learned-SDF weights (NlotMlp handle).  arith: "split_bf16" (the default: three-way bf16 operand
     split, six MFMA products per fp32 product) or "f32" (v_mfma_f32 products, the reference's fp32 net); both fp32
     arithmetic, differing at the rounding level (include/nlot.h, NLOT_MLP_ARITH_*).  "seq" (ReLU nets; tests): every
-    sum a sequential fp32 FMA chain in index order, the oracle's default order, one thread per point."""
+    sum a sequential fp32 FMA chain in index order, the oracle's default order, one thread per point.  "hdual_mfma"
+    (smooth activations, hidden width 128 with 1-2 HxH layers or 64 with 1-4): value, gradient and Hessian carried
+    forward as hyper-duals through v_mfma_f32 products (mlp_hdual); opt-in, a smooth net with any other arith takes
+    the scalar-FMA kernel mlp_smooth."""
 
-    ARITH = {"split_bf16": 0, "f32": 1, "seq": 2}
+    ARITH = {"split_bf16": 0, "f32": 1, "seq": 2, "hdual_mfma": 3}
 
     def __init__(self, weights: MlpWeights, arith: str = "split_bf16"):
         require_gpu()

@@ -1,0 +1,79 @@
+"""Launch time of a smooth-activation learned SDF: mlp_smooth (scalar FMA) against mlp_hdual (MFMA hyper-duals,
+DeviceMlp(w, "hdual_mfma")).
+
+Two nets of the artefact's shape: the artefact's FourierMLP 2-128-128-1 with tanh hidden layers, and a seeded SIREN
+2-128-128-1.  Per net, full (value, gradient, Hessian) and value launches at --points points, timed with device events
+around --reps launches after --warmup of them.  The kernels alternate mlp_smooth, mlp_hdual, mlp_smooth in one
+process, so that the spread of the two mlp_smooth runs bounds what the machine itself contributes.  Achieved FLOP/s
+counts the HxH layers' products only, 2 NC L H^2 per point (NC = 6 components full, 1 value), against the f32 MFMA
+peak of 157.3 TFLOP/s.  Writes one JSON to profiles/smooth_mlp_bench.json and prints it.
+
+    python scripts/smooth_mlp_bench.py [--points 1000000] [--reps 20] [--warmup 3]
+"""
+import argparse
+import dataclasses
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK_TFLOPS = 157.3  # v_mfma_f32_16x16x4_f32: 256 FLOP / cycle / CU x 256 CUs x 2.4 GHz
+
+
+def time_ms(mlp, pts, full, reps, warmup):
+    import torch
+
+    from nlotrajectories_amd.ops import sdf_mlp_eval
+
+    for _ in range(warmup):
+        sdf_mlp_eval(mlp, pts, derivatives=full)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        sdf_mlp_eval(mlp, pts, derivatives=full)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=1000000)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+
+    from nlotrajectories_amd import _abi
+    from nlotrajectories_amd.nn import SIREN, MlpWeights
+    from nlotrajectories_amd.ops import DeviceMlp
+
+    assert torch.cuda.is_available(), "smooth_mlp_bench.py measures on the GPU"
+    torch.manual_seed(0)
+    nets = {"fourier_tanh_2-128-128-1": dataclasses.replace(MlpWeights.artefact(), act=_abi.ACT_TANH),
+            "siren_2-128-128-1": MlpWeights.from_module(SIREN(2, 128, 1, num_layers=3, omega_0=30))}
+    pts = torch.tensor(np.random.default_rng(0).uniform(-0.5, 1.5, (a.points, 2)).astype(np.float32), device="cuda")
+    out = dict(points=a.points, reps=a.reps, warmup=a.warmup, peak_tflops=PEAK_TFLOPS, nets={})
+    for name, w in nets.items():
+        smooth, hdual = DeviceMlp(w, "f32"), DeviceMlp(w, "hdual_mfma")
+        res = {}
+        for launch, full in (("full", True), ("value", False)):
+            sa, hd, sb = (time_ms(m, pts, full, a.reps, a.warmup) for m in (smooth, hdual, smooth))
+            flop = 2.0 * (6 if full else 1) * w.n_hidden * w.hidden ** 2 * a.points
+            res[launch] = dict(mlp_smooth_ms=[sa, sb], mlp_smooth_spread_ms=abs(sa - sb), mlp_hdual_ms=hd,
+                               speedup=min(sa, sb) / hd, flop_per_point=flop / a.points,
+                               mlp_hdual_tflops=flop / hd * 1e-9, mlp_hdual_share_of_peak=flop / hd * 1e-9 / PEAK_TFLOPS,
+                               mlp_smooth_tflops=flop / min(sa, sb) * 1e-9)
+        out["nets"][name] = res
+    text = json.dumps(out)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "smooth_mlp_bench.json"), "w") as f:
+        f.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
