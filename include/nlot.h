@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 21
+#define NLOT_ABI_VERSION 22
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -221,11 +221,17 @@ NlotMlp* nlot_mlp_create(const NlotMlpDesc* desc);
  *   NLOT_MLP_ARITH_HDUAL_MFMA  (ABI v21; smooth activations: tanh, sigmoid, leaky ReLU, sine) value, gradient and Hessian
  *                              carried forward as hyper-duals through v_mfma_f32 products, every HxH layer resident in
  *                              LDS: hidden width 128 with 1-2 HxH layers or 64 with 1-4.  Opt-in: a smooth net created
- *                              with any other value takes the scalar-FMA kernel.  Refused for ReLU nets */
+ *                              with any other value takes the scalar-FMA kernel.  Refused for ReLU nets
+ *   NLOT_MLP_ARITH_HDUAL_STREAM (ABI v22; smooth activations) the same hyper-dual v_mfma_f32 arithmetic for the shapes that
+ *                              do not fit in LDS: the waves of a block split a layer's units, the activations live in
+ *                              LDS and the HxH weights stream from L2 in a fragment order made at creation.  Hidden
+ *                              width 64, 128 or 256 with 1-4 HxH layers.  Opt-in like NLOT_MLP_ARITH_HDUAL_MFMA; refused
+ *                              for ReLU nets and for nets without an HxH layer */
 #define NLOT_MLP_ARITH_SPLIT_BF16 0
 #define NLOT_MLP_ARITH_F32 1
 #define NLOT_MLP_ARITH_SEQ 2
 #define NLOT_MLP_ARITH_HDUAL_MFMA 3
+#define NLOT_MLP_ARITH_HDUAL_STREAM 4
 NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* desc, int32_t arith);
 void nlot_mlp_destroy(NlotMlp* mlp);
 

@@ -118,7 +118,7 @@ def lib():
     L.nlot_sdf_batch_loss.restype = C.c_int32
     L.nlot_casadi_bind.argtypes = [vp]
     L.nlot_casadi_bind.restype = C.c_int32
-    if L.nlot_abi_version() != 21:
+    if L.nlot_abi_version() != 22:
         raise NlotError("libnlot.so ABI version mismatch")
     _lib = L
     return L

@@ -90,7 +90,7 @@ struct MlpDev {
     int in_kind;     // NLOT_MLP_IN_*
     int H;           // hidden width
     int n_hidden;    // HxH layers
-    int act;         // NLOT_ACT_* (ReLU: the MFMA kernels; smooth activations: mlp_smooth, or mlp_hdual by arith)
+    int act;         // NLOT_ACT_* (ReLU: the MFMA kernels; smooth activations: mlp_smooth, or mlp_hdual[_stream] by arith)
     float scale;     // fourier scale; omega_0 for NLOT_ACT_SINE
     float b_out;
     const float* A;     // [2][H]
@@ -100,6 +100,9 @@ struct MlpDev {
     const float* w_out; // [H]
     const void* Wp;     // [3][H][H] bf16 planes (hi, mid, lo) of layer 0, for the split-bf16 value kernel
     const float* Wt;    // [n_hidden][H][H] (in, out): transposed HxH layers for mlp_smooth (smooth nets only)
+    // NLOT_MLP_ARITH_HDUAL_STREAM only: the HxH layers in MFMA fragment order [n_hidden][4 waves][H/16 T][H/64 t][64 lanes]
+    // [4], lane (pn, lg) holding W[16 (wave H/64 + t) + pn][16 T + 4 lg .. +3]
+    const float* Wf;
 };
 
 // Output addressing of the MLP kernel: element q of point i goes to ptr_q[i * stride_q].

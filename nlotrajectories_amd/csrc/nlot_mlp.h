@@ -1,5 +1,6 @@
 // What the learned-SDF MLP kernel families share (internal): nlot_mlp_f32.hip, nlot_mlp_bf16.hip, nlot_mlp_stream.hip,
-// nlot_mlp_hdual.hip and nlot_mlp_ref.hip hold one family each behind the launcher declared here; nlot_mlp.hip chooses among them.
+// nlot_mlp_hdual.hip, nlot_mlp_hdual_stream.hip and nlot_mlp_ref.hip hold one family each behind the launcher declared
+// here; nlot_mlp.hip chooses among them.
 #pragma once
 #include "nlot_internal.h"
 
@@ -94,7 +95,8 @@ __device__ __forceinline__ void input_contract(float ax, float ay, float z, floa
     hyy = fmaf(ay * ay, c2, hyy);
 }
 
-// s(z), s'(z), s''(z) of the activation: mlp_smooth and mlp_hdual evaluate them by these expressions
+// s(z), s'(z), s''(z) of the activation: mlp_smooth, mlp_hdual and mlp_hdual_stream evaluate them by these
+// expressions
 __device__ __forceinline__ void act3(int act, float omega, float z, float& s, float& d1, float& d2) {
     if (act == NLOT_ACT_TANH) {
         s = tanhf(z);
@@ -118,6 +120,18 @@ __device__ __forceinline__ void act3(int act, float omega, float z, float& s, fl
         s = z > 0.f ? z : 0.f;
         d1 = z > 0.f ? 1.f : 0.f;
         d2 = 0.f;
+    }
+}
+
+// f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>), in order.  The tile loops of mlp_hdual and
+// mlp_hdual_stream whose bodies hold the activation are unrolled this way, not by #pragma unroll: sinf / cosf with
+// their large-argument paths make the unrolled body larger than the pragma's size threshold, the loop then stays a
+// loop, and the register arrays it indexes go to scratch.
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (N > 0) {
+        static_for<N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
     }
 }
 
@@ -149,9 +163,19 @@ inline const char* hdual_refusal(int act, int H, int n_hidden) {
     return nullptr;
 }
 
+// NLOT_MLP_ARITH_HDUAL_STREAM keeps the activations in LDS and streams the weights (nlot_mlp_hdual_stream.hip): null
+// when mlp_hdual_stream serves the net, else why not (nlot_mlp_create_ex refuses with it before any device call)
+inline const char* hdual_stream_refusal(int act, int H, int n_hidden) {
+    if (act == NLOT_ACT_RELU || (H != 64 && H != 128 && H != 256) || n_hidden < 1 || n_hidden > kMaxStreamLayers)
+        return "NLOT_MLP_ARITH_HDUAL_STREAM serves smooth activations (tanh, sigmoid, leaky ReLU, sine) with hidden width "
+               "64, 128 or 256 and 1-4 HxH layers; ReLU nets take the reverse-sweep arithmetics, a smooth net without "
+               "HxH layers NLOT_MLP_ARITH_F32 (mlp_smooth)";
+    return nullptr;
+}
+
 // One launcher per family, arguments as launch_mlp_strided's, which has checked w.n_hidden for the family: f32 takes
-// H <= 128 with 1 or 2 HxH layers, bf16 H = 128 with one HxH layer and w.Wp, hdual what hdual_refusal passes, the
-// others every width
+// H <= 128 with 1 or 2 HxH layers, bf16 H = 128 with one HxH layer and w.Wp, hdual what hdual_refusal passes,
+// hdual_stream what hdual_stream_refusal passes and w.Wf, the others every width
 int launch_mlp_f32(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                    const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_bf16(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
@@ -162,6 +186,8 @@ int launch_mlp_smooth(const MlpDev& w, const float* pts, int64_t n, const int* n
                       const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_hdual(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                      const float* lam, const MlpOut& out, bool full, hipStream_t stream);
+int launch_mlp_hdual_stream(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
+                            const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_seq(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                    const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 

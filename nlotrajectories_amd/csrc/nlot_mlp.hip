@@ -39,6 +39,8 @@ int launch_mlp_strided(const MlpDev& w, const float* pts, int64_t n, const int* 
         return launch_mlp_seq(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
     if (w.arith == NLOT_MLP_ARITH_HDUAL_MFMA)  // smooth nets whose layers fit in LDS (nlot_mlp_create_ex checks)
         return launch_mlp_hdual(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
+    if (w.arith == NLOT_MLP_ARITH_HDUAL_STREAM)  // every smooth net with HxH layers (nlot_mlp_create_ex checks)
+        return launch_mlp_hdual_stream(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
     if (w.act != NLOT_ACT_RELU) {  // smooth activations: forward hyper-duals (the ReLU masks / reuse do not apply)
         if (w.n_hidden < 0 || w.n_hidden > kMaxStreamLayers) {
             set_error("MLP kernel: 0 to 4 hidden HxH layers are supported for smooth activations");
@@ -71,9 +73,9 @@ extern "C" NlotMlp* nlot_mlp_create(const NlotMlpDesc* d) { return nlot_mlp_crea
 extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
     using namespace nlot;
     if (arith != NLOT_MLP_ARITH_SPLIT_BF16 && arith != NLOT_MLP_ARITH_F32 && arith != NLOT_MLP_ARITH_SEQ &&
-        arith != NLOT_MLP_ARITH_HDUAL_MFMA) {
-        set_error("nlot_mlp_create_ex: arith must be NLOT_MLP_ARITH_SPLIT_BF16, NLOT_MLP_ARITH_F32, NLOT_MLP_ARITH_SEQ or "
-                  "NLOT_MLP_ARITH_HDUAL_MFMA");
+        arith != NLOT_MLP_ARITH_HDUAL_MFMA && arith != NLOT_MLP_ARITH_HDUAL_STREAM) {
+        set_error("nlot_mlp_create_ex: arith must be NLOT_MLP_ARITH_SPLIT_BF16, NLOT_MLP_ARITH_F32, NLOT_MLP_ARITH_SEQ, "
+                  "NLOT_MLP_ARITH_HDUAL_MFMA or NLOT_MLP_ARITH_HDUAL_STREAM");
         return nullptr;
     }
     if (arith == NLOT_MLP_ARITH_SEQ && d && d->act != NLOT_ACT_RELU) {
@@ -102,12 +104,20 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
             return nullptr;
         }
     }
+    if (arith == NLOT_MLP_ARITH_HDUAL_STREAM) {
+        if (const char* why = hdual_stream_refusal(d->act, d->hidden, d->n_hidden)) {
+            set_error(std::string("nlot_mlp_create_ex: ") + why);
+            return nullptr;
+        }
+    }
     const int H = d->hidden, L = d->n_hidden;
     const size_t nA = 2 * H, nb0 = H, nW = (size_t)L * H * H, nb = (size_t)L * H, nw = H;
     const bool split = arith == NLOT_MLP_ARITH_SPLIT_BF16;
     const size_t nWp = split ? (size_t)3 * H * H / 2 : 0;  // bf16 planes of layer 0, in float units
-    const size_t nWt = smooth && arith != NLOT_MLP_ARITH_HDUAL_MFMA ? nW : 0;  // transposed HxH layers (mlp_smooth)
-    const size_t total = nA + nb0 + nW + nb + nw + nWp + nWt + 4;
+    const bool stream = arith == NLOT_MLP_ARITH_HDUAL_STREAM;
+    const size_t nWt = smooth && arith != NLOT_MLP_ARITH_HDUAL_MFMA && !stream ? nW : 0;  // transposed HxH layers (mlp_smooth)
+    const size_t nWf = stream ? nW : 0;  // HxH layers in fragment order (mlp_hdual_stream)
+    const size_t total = nA + nb0 + nW + nb + nw + nWp + nWt + nWf + 4;
     float* blk = nullptr;
     if (hipMalloc(&blk, total * sizeof(float)) != hipSuccess) {
         set_error("nlot_mlp_create: hipMalloc failed");
@@ -169,6 +179,21 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
             for (int o = 0; o < H; ++o)
                 for (int k = 0; k < H; ++k) wt[(size_t)l * H * H + (size_t)k * H + o] = d->W[(size_t)l * H * H + (size_t)o * H + k];
         m->dev.Wt = put(wt.data(), nWt);
+    }
+    m->dev.Wf = nullptr;
+    if (nWf) {  // [l][wave][T][t][lane][4]: the A quad a wave of mlp_hdual_stream loads for input tile T, output tile t
+        std::vector<float> wf(nW);
+        const int NT = H / 16, NQ = H / 64;
+        size_t q = 0;
+        for (int l = 0; l < L; ++l)
+            for (int wave = 0; wave < 4; ++wave)
+                for (int T = 0; T < NT; ++T)
+                    for (int t = 0; t < NQ; ++t)
+                        for (int lane = 0; lane < 64; ++lane)
+                            for (int j = 0; j < 4; ++j)
+                                wf[q++] = d->W[(size_t)l * H * H + (size_t)(16 * (wave * NQ + t) + (lane & 15)) * H +
+                                               16 * T + 4 * (lane >> 4) + j];
+        m->dev.Wf = put(wf.data(), nWf);
     }
     if (hipDeviceSynchronize() != hipSuccess) {
         set_error("nlot_mlp_create: copy failed");

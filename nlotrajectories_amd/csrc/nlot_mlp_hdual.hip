@@ -35,18 +35,6 @@ __host__ __device__ constexpr size_t hdual_lds_floats(int H, int L) {
     return (size_t)L * H * hdual_stride(H) + (size_t)4 * H + (size_t)L * H;
 }
 
-// f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>), in order.  The two tile loops whose bodies hold the
-// activation are unrolled this way, not by #pragma unroll: sinf / cosf with their large-argument paths make the
-// unrolled body larger than the pragma's size threshold, the loop then stays a loop, and the register arrays it
-// indexes go to scratch.
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
-
 template <int H, int ACT, bool FULL>
 __global__ __launch_bounds__(256, 1) void mlp_hdual(MlpDev w, const float* __restrict__ pts, int64_t cnt_host,
                                                     const int* __restrict__ cnt_dev, int P_per, int64_t ld,

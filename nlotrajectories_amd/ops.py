@@ -18,9 +18,11 @@ class DeviceMlp:
     sum a sequential fp32 FMA chain in index order, the oracle's default order, one thread per point.  "hdual_mfma"
     (smooth activations, hidden width 128 with 1-2 HxH layers or 64 with 1-4): value, gradient and Hessian carried
     forward as hyper-duals through v_mfma_f32 products (mlp_hdual); opt-in, a smooth net with any other arith takes
-    the scalar-FMA kernel mlp_smooth."""
+    the scalar-FMA kernel mlp_smooth.  "hdual_stream" (smooth activations, hidden width 64, 128 or 256 with 1-4 HxH
+    layers): the same arithmetic with the activations in LDS and the weights streamed from L2 (mlp_hdual_stream), for
+    the shapes "hdual_mfma" refuses; opt-in as well."""
 
-    ARITH = {"split_bf16": 0, "f32": 1, "seq": 2, "hdual_mfma": 3}
+    ARITH = {"split_bf16": 0, "f32": 1, "seq": 2, "hdual_mfma": 3, "hdual_stream": 4}
 
     def __init__(self, weights: MlpWeights, arith: str = "split_bf16"):
         require_gpu()

@@ -8,7 +8,12 @@ process, so that the spread of the two mlp_smooth runs bounds what the machine i
 counts the HxH layers' products only, 2 NC L H^2 per point (NC = 6 components full, 1 value), against the f32 MFMA
 peak of 157.3 TFLOP/s.  Writes one JSON to profiles/smooth_mlp_bench.json and prints it.
 
-    python scripts/smooth_mlp_bench.py [--points 1000000] [--reps 20] [--warmup 3]
+--arith hdual_stream times mlp_hdual_stream (DeviceMlp(w, "hdual_stream"): activations in LDS, weights streamed from
+L2) in the same mlp_smooth / kernel / mlp_smooth alternation on the shapes mlp_hdual cannot hold, a tanh 2-256x4-1 (the
+stress shape) and a tanh net of H = 128 with 4 HxH layers, and on the artefact-shaped Fourier-tanh 2-128-128-1, where
+mlp_hdual is timed as a third contestant.  That mode writes profiles/smooth_mlp_stream_bench.json.
+
+    python scripts/smooth_mlp_bench.py [--arith hdual_mfma|hdual_stream] [--points 1000000] [--reps 20] [--warmup 3]
 """
 import argparse
 import dataclasses
@@ -38,8 +43,41 @@ def time_ms(mlp, pts, full, reps, warmup):
     return a.elapsed_time(b) / reps
 
 
+def stream_bench(a, pts):
+    """The --arith hdual_stream mode: {net: {launch: times}}."""
+    import torch
+
+    from nlotrajectories_amd import _abi
+    from nlotrajectories_amd.nn import MlpWeights, MultiLayerPerceptron
+    from nlotrajectories_amd.ops import DeviceMlp
+
+    torch.manual_seed(0)
+    nets = {"mlp_tanh_2-256x4-1": MlpWeights.from_module(MultiLayerPerceptron(2, 256, 1, 4, "Tanh")),
+            "mlp_tanh_2-128x5-1": MlpWeights.from_module(MultiLayerPerceptron(2, 128, 1, 5, "Tanh")),
+            "fourier_tanh_2-128-128-1": dataclasses.replace(MlpWeights.artefact(), act=_abi.ACT_TANH)}
+    out = {}
+    for name, w in nets.items():
+        smooth, stream = DeviceMlp(w, "f32"), DeviceMlp(w, "hdual_stream")
+        hdual = DeviceMlp(w, "hdual_mfma") if w.n_hidden == 1 else None  # the one shape here the resident kernel holds
+        res = {}
+        for launch, full in (("full", True), ("value", False)):
+            sa, st, sb = (time_ms(m, pts, full, a.reps, a.warmup) for m in (smooth, stream, smooth))
+            flop = 2.0 * (6 if full else 1) * w.n_hidden * w.hidden ** 2 * a.points
+            res[launch] = dict(mlp_smooth_ms=[sa, sb], mlp_smooth_spread_ms=abs(sa - sb), mlp_hdual_stream_ms=st,
+                               speedup=min(sa, sb) / st, flop_per_point=flop / a.points,
+                               mlp_hdual_stream_tflops=flop / st * 1e-9,
+                               mlp_hdual_stream_share_of_peak=flop / st * 1e-9 / PEAK_TFLOPS,
+                               mlp_smooth_tflops=flop / min(sa, sb) * 1e-9)
+            if hdual:
+                hd = time_ms(hdual, pts, full, a.reps, a.warmup)
+                res[launch].update(mlp_hdual_ms=hd, stream_over_hdual=st / hd)
+        out[name] = res
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arith", choices=["hdual_mfma", "hdual_stream"], default="hdual_mfma")
     ap.add_argument("--points", type=int, default=1000000)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -57,6 +95,9 @@ def main():
             "siren_2-128-128-1": MlpWeights.from_module(SIREN(2, 128, 1, num_layers=3, omega_0=30))}
     pts = torch.tensor(np.random.default_rng(0).uniform(-0.5, 1.5, (a.points, 2)).astype(np.float32), device="cuda")
     out = dict(points=a.points, reps=a.reps, warmup=a.warmup, peak_tflops=PEAK_TFLOPS, nets={})
+    if a.arith == "hdual_stream":
+        nets = {}
+        out.update(arith=a.arith, nets=stream_bench(a, pts))
     for name, w in nets.items():
         smooth, hdual = DeviceMlp(w, "f32"), DeviceMlp(w, "hdual_mfma")
         res = {}
@@ -70,7 +111,8 @@ def main():
         out["nets"][name] = res
     text = json.dumps(out)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "smooth_mlp_bench.json"), "w") as f:
+    name = "smooth_mlp_stream_bench.json" if a.arith == "hdual_stream" else "smooth_mlp_bench.json"
+    with open(os.path.join(ROOT, "profiles", name), "w") as f:
         f.write(text + "\n")
     print(text)
 
