@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 22
+#define NLOT_ABI_VERSION 23
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -630,6 +630,61 @@ int32_t nlot_sdf_train_steps(const NlotSdfTrainOptions* opt, float* state, const
  * parameters of `state` are read.  Errors as nlot_sdf_train_steps' for opt, the pointers, M and n. */
 int32_t nlot_sdf_batch_loss(const NlotSdfTrainOptions* opt, const float* state, const float* pts, const float* target,
                             int64_t n, float* batch_loss, int64_t M, void* stream);
+
+/* ---- certified clearance of the interpolated plan by Lipschitz branch-and-bound (ABI v23) -----------
+ * nlot_verify_batch samples: its clearance is an upper bound of the plan's true clearance and proves nothing
+ * (DESIGN.md section 10).  nlot_certify_batch brackets the true minimum: it refines boxes of (interval, footprint edge,
+ * tau range, edge-parameter range) where the clearance is small, bounding the exact SDF (1-Lipschitz) on a box by its
+ * value at the centre minus the box's radius.  The motion is nlot_verify_batch's: on interval k
+ * the pose is X_k + tau (X_{k+1} - X_k), tau in [0, 1], components 0, 1 and (polygon body) the heading 2, no angle
+ * wrapped.  The domain is every tau of every interval times the footprint's boundary: the one point of
+ * NLOT_SHAPE_DOT, or every point c(t) = (1 - t) c_i + t c_{i+1}, t in [0, 1], of every edge i of the polygon.  It
+ * certifies that interpolated plan, not the rolled flow of nlot_rollout_batch / nlot_track_batch; it is sound up to the
+ * fp64 rounding of the exact SDF (about 1e-15; the bounds are not inflated); the containment argument assumes a convex
+ * footprint. */
+typedef struct NlotCertifyOptions {
+    double tol;            /* refine until upper - lower <= tol; > 0, finite (default 1e-3) */
+    double clearance_min;  /* the verdict's threshold (0) */
+    int32_t decide;        /* 0 (default): tighten the bracket to tol.
+                              1: only decide the verdict: a box also retires once its bound >= clearance_min, and
+                                 refinement stops as soon as upper < clearance_min */
+    int32_t max_evals;     /* hard cap on exact-SDF evaluations per instance spent refining;
+                              0 (default) = min(2^24, 4096 + 256 * N * n_edges), n_edges = n_body (1 for a dot);
+                              else 1 .. 2^24 */
+} NlotCertifyOptions;
+#define NLOT_CERTIFY_COLLISION 1   /* upper < clearance_min: a witness point exists */
+#define NLOT_CERTIFY_CONTAINS 2    /* an obstacle's centre (circle, square) or vertex (polygon, trapezoid) lies strictly
+                                      inside the footprint at knot 0 (polygon bodies) */
+#define NLOT_CERTIFY_UNDECIDED 4   /* lower < clearance_min <= upper */
+#define NLOT_CERTIFY_BUDGET 8      /* refinement was cut short by max_evals, by the box stack's capacity (1024 boxes) or by
+                                      the bisection depth (30 per dimension): the bounds are valid, only looser */
+#define NLOT_CERTIFY_NONFINITE 32  /* a non-finite entry in the instance's X: lower, upper and tau are NaN, where is -1,
+                                      evals is 0 and no other flag is set */
+/* Fill `opt` with the defaults documented above. */
+void nlot_default_certify_options(NlotCertifyOptions* opt);
+
+/* Bracket the clearance of B plans of `prob` against the scene's EXACT SDF in prob->obs, whatever prob->sdf_kind says
+ * (as nlot_verify_batch).  With f the exact SDF at pos(tau) + R(theta(tau)) c(t), per instance:
+ *   lower, upper  lower <= min f <= upper over the whole domain.  upper is f at an actual domain point; without
+ *              NLOT_CERTIFY_BUDGET and with decide == 0, upper - lower <= tol
+ *   where, tau the interval and parameter of upper's point, the lowest (where, tau) on exact ties among the points
+ *              evaluated; knot k < N counts as (k, 0) and knot N as (N - 1, 1)
+ *   evals      exact-SDF evaluations spent: the (N + 1) x corners seed samples, the refinement (<= max_evals) and the
+ *              drain (one per box left when refinement is cut short or, with decide, stops early)
+ *   flags      NLOT_CERTIFY_* bits.  0 = proven clear: every point of the footprint's boundary keeps clearance >=
+ *              clearance_min at every instant of the interpolated motion, and no obstacle centre / vertex is inside the
+ *              footprint at knot 0, which (an obstacle would have to cross the boundary to get in) rules out
+ *              containment at every later instant too
+ *   X [B][N+1][nx] fp64 device; the six outputs [B] device, all required.
+ * An instance's outputs depend on that instance's inputs only: they are bitwise the same whatever B is and wherever
+ * in the batch the instance sits (the search order is fixed: a LIFO box stack, children placed by ballot rank).
+ * Asynchronous on `stream`; no workspace, no global state (a stream-ordered temporary holds the problem).
+ * NLOT_ERR_INVALID before any device call for: null prob or opt; tol not > 0 or not finite; a non-finite
+ * clearance_min; decide outside {0, 1}; max_evals outside 0 .. 2^24; n_obs == 0; an invalid problem (the checks of
+ * nlot_verify_batch); B outside 1 .. 2^26; a null X or output. */
+int32_t nlot_certify_batch(const NlotProblem* prob, const NlotCertifyOptions* opt, const double* X, double* lower,
+                           double* upper, int32_t* where, double* tau, int32_t* evals, int32_t* flags, int64_t B,
+                           void* stream);
 
 casadi_int_t nn_sdf_n_in(void);
 casadi_int_t nn_sdf_n_out(void);

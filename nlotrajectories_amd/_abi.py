@@ -140,6 +140,22 @@ def verify_options(sub=8, edge_points=3, clearance_min=0.0, defect_tol=1e-4, bou
                              defect_tol=float(defect_tol), bound_tol=float(bound_tol))
 
 
+# nlot_certify_batch (include/nlot.h, ABI v23): flag bits of the per-instance verdict
+CERTIFY_COLLISION, CERTIFY_CONTAINS, CERTIFY_UNDECIDED, CERTIFY_BUDGET, CERTIFY_NONFINITE = 1, 2, 4, 8, 32
+CERTIFY_FLAG_NAMES = {1: "collision", 2: "contains", 4: "undecided", 8: "budget", 32: "nonfinite"}
+
+
+class NlotCertifyOptions(C.Structure):
+    """include/nlot.h NlotCertifyOptions."""
+    _fields_ = [("tol", C.c_double), ("clearance_min", C.c_double), ("decide", C.c_int32), ("max_evals", C.c_int32)]
+
+
+def certify_options(tol=1e-3, clearance_min=0.0, decide=False, max_evals=0) -> NlotCertifyOptions:
+    """The defaults of nlot_default_certify_options (max_evals 0: the library's default budget)."""
+    return NlotCertifyOptions(tol=float(tol), clearance_min=float(clearance_min), decide=int(bool(decide)),
+                              max_evals=int(max_evals))
+
+
 # nlot_rollout_batch (include/nlot.h, ABI v17): flag bits of the per-instance verdict
 ROLLOUT_COLLISION, ROLLOUT_CONTAINS, ROLLOUT_DEVIATION, ROLLOUT_GOAL, ROLLOUT_NONFINITE, ROLLOUT_DIVERGED = 1, 2, 4, 8, 32, 64
 ROLLOUT_FLAG_NAMES = {1: "collision", 2: "contains", 4: "deviation", 8: "goal", 32: "nonfinite", 64: "diverged"}

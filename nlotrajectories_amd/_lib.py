@@ -28,6 +28,7 @@ EXPORTED = [
     "nlot_scene_sdf_eval", "nlot_default_sdf_metrics_options", "nlot_sdf_metrics",
     "nlot_default_tvlqr_options", "nlot_tvlqr_batch", "nlot_default_track_options", "nlot_track_batch",
     "nlot_sdf_train_default_options", "nlot_sdf_train_state_floats", "nlot_sdf_train_steps", "nlot_sdf_batch_loss",
+    "nlot_default_certify_options", "nlot_certify_batch",
 ]
 
 
@@ -116,9 +117,14 @@ def lib():
     L.nlot_sdf_train_steps.restype = C.c_int32
     L.nlot_sdf_batch_loss.argtypes = [C.POINTER(_abi.NlotSdfTrainOptions), vp, vp, vp, C.c_int64, vp, C.c_int64, vp]
     L.nlot_sdf_batch_loss.restype = C.c_int32
+    L.nlot_default_certify_options.argtypes = [C.POINTER(_abi.NlotCertifyOptions)]
+    L.nlot_default_certify_options.restype = None
+    L.nlot_certify_batch.argtypes = [C.POINTER(_abi.NlotProblem), C.POINTER(_abi.NlotCertifyOptions), vp, vp, vp, vp,
+                                     vp, vp, vp, C.c_int64, vp]
+    L.nlot_certify_batch.restype = C.c_int32
     L.nlot_casadi_bind.argtypes = [vp]
     L.nlot_casadi_bind.restype = C.c_int32
-    if L.nlot_abi_version() != 22:
+    if L.nlot_abi_version() != 23:
         raise NlotError("libnlot.so ABI version mismatch")
     _lib = L
     return L

@@ -21,6 +21,8 @@ Differences from the reference, all loud:
   * --track (off by default) computes the time-varying LQR gains about the returned plan and rolls it with the loop
     closed (tracking.py: feedback sampled at the knots, clamped to the control bounds) and prints five more lines,
     after --rollout's; nothing else changes;
+  * --certify (off by default) brackets the interpolated plan's true clearance by Lipschitz branch-and-bound
+    (certify.py) and prints two more lines, after --verify's; nothing else changes;
   * --metrics-device gpu (default host) computes the SDF-quality metrics on the device (scene_gpu.scene_metrics: the
     solver's own scene functions and a brute-force nearest-neighbour kernel) instead of scene.py's numpy; the CSV is
     the same to rounding.  --train-sdf-device gpu does the same for the training targets of `--weights train`.
@@ -89,6 +91,20 @@ def _print_verification(prob, r, x0, xg, sub, edge_points):
     print("Collision-free:", not flags & (_abi.VERIFY_COLLISION | _abi.VERIFY_CONTAINS | _abi.VERIFY_NONFINITE))
 
 
+def _print_certificate(prob, r, tol):
+    """--certify: the proven bracket of the interpolated plan's clearance (certify.py), for a failed solve too."""
+    from .certify import certify_batch
+
+    v = certify_batch(prob, r["X"], tol=tol)
+    flags = int(v["flags"][0])
+    print(f"Certified clearance: [{float(v['lower'][0])}, {float(v['upper'][0])}] at knot {int(v['where'][0])} + "
+          f"{float(v['tau'][0])} ({int(v['evals'][0])} evaluations)")
+    verdict = ("clear" if flags == 0 else
+               "nonfinite" if flags & _abi.CERTIFY_NONFINITE else
+               "collision" if flags & (_abi.CERTIFY_COLLISION | _abi.CERTIFY_CONTAINS) else "undecided")
+    print("Certified verdict:", verdict)
+
+
 def _print_rollout(prob, r, xg, substeps, edge_points):
     """--rollout: the returned controls rolled through the continuous dynamics (rollout.py), for a failed solve too."""
     from .rollout import rollout_batch
@@ -122,11 +138,13 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
                   options=None, metrics=True, verify=False, verify_sub=8, verify_edge_points=3, rollout=False,
                   rollout_substeps=8, rollout_edge_points=3, metrics_device="host", train_sdf_device="host",
                   train_backend="torch", mlp_arith="split_bf16",
-                  track=False, track_substeps=8, track_edge_points=3, track_q=1.0, track_r=1.0, track_qf=1.0):
+                  track=False, track_substeps=8, track_edge_points=3, track_q=1.0, track_r=1.0, track_qf=1.0,
+                  certify=False, certify_tol=1e-3):
     """Returns (X_opt [nx, N+1], U_opt [nu, N], status str) like RunBenchmark.run (runner.py:148-153).
     verify=True also prints the trajectory's exact clearance, dynamics defect and collision verdict; rollout=True the
     clearance, deviation from the plan and goal error of the controls rolled through the continuous dynamics;
-    track=True the same and the saturated knots of the plan tracked with its TVLQR gains.  mlp_arith: the learned SDF's
+    track=True the same and the saturated knots of the plan tracked with its TVLQR gains; certify=True the proven
+    bracket of the interpolated plan's clearance and its verdict.  mlp_arith: the learned SDF's
     arithmetic (DeviceMlp.ARITH; "hdual_mfma" puts a smooth-activation net on the MFMA hyper-dual kernel,
     "hdual_stream" on its streamed-weight variant)."""
     config_path = Path(config_path)
@@ -178,6 +196,8 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
             print("Dynamics violation:", np.linalg.norm(X[:, 1:] - X[:, :-1] - prob.dt * _f(prob, X[:, :-1], U)))
             if verify:
                 _print_verification(prob, r, x0, xg, verify_sub, verify_edge_points)
+            if certify:
+                _print_certificate(prob, r, certify_tol)
             if rollout:
                 _print_rollout(prob, r, xg, rollout_substeps, rollout_edge_points)
             if track:
@@ -195,6 +215,8 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
     print("Final state:", X[:, -1])
     if verify:
         _print_verification(prob, r, x0, xg, verify_sub, verify_edge_points)
+    if certify:
+        _print_certificate(prob, r, certify_tol)
     if rollout:
         _print_rollout(prob, r, xg, rollout_substeps, rollout_edge_points)
     if track:
@@ -249,6 +271,10 @@ def _parser():
                          "footprint's edges, and its dynamics defect (verify.py)")
     ap.add_argument("--verify-sub", type=int, default=8, help="--verify: poses sampled per interval")
     ap.add_argument("--verify-edge-points", type=int, default=3, help="--verify: interior points per footprint edge")
+    ap.add_argument("--certify", action="store_true",
+                    help="bracket the interpolated plan's true clearance by Lipschitz branch-and-bound and print the "
+                         "proven verdict (certify.py)")
+    ap.add_argument("--certify-tol", type=float, default=1e-3, help="--certify: the bracket's width")
     ap.add_argument("--rollout", action="store_true",
                     help="roll the returned controls through the continuous dynamics (sub-stepped RK4, zero-order hold, "
                          "open loop) and report the rolled motion's clearance, deviation and goal error (rollout.py)")
@@ -291,7 +317,8 @@ def main(argv=None):
                   metrics_device=a.metrics_device, train_sdf_device=a.train_sdf_device,
                   train_backend=a.train_backend, mlp_arith=a.mlp_arith, track=a.track,
                   track_substeps=a.track_substeps, track_edge_points=a.track_edge_points, track_q=_weight(a.track_q),
-                  track_r=_weight(a.track_r), track_qf=_weight(a.track_qf))
+                  track_r=_weight(a.track_r), track_qf=_weight(a.track_qf), certify=a.certify,
+                  certify_tol=a.certify_tol)
 
 
 if __name__ == "__main__":

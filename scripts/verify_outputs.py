@@ -17,6 +17,10 @@ and how many of the instances verify_batch passes the rollout flags.
 (nlot_tvlqr_batch) and rolls it with the loop closed (nlot_track_batch); it adds one key `track` with the same fields
 as `rollout` for the closed loop, the share of the solved instances that saturate, the quantiles of the saturated-knot
 count, and the gains' status counts.
+
+--certify [--certify-tol 1e-3] also brackets every dumped plan's true clearance (nlot_certify_batch) and adds one key
+`certify`: over the solved instances the counts of proven clear / collision / undecided verdicts, the same split of the
+instances verify_batch passes, the share cut short by the budget and the mean and largest evaluation count.
 """
 import argparse
 import json
@@ -52,6 +56,8 @@ def main(argv=None):
     ap.add_argument("--track-q", type=float, nargs="+", default=[1.0], help="one value, or one per state component")
     ap.add_argument("--track-r", type=float, nargs="+", default=[1.0], help="one value, or one per control")
     ap.add_argument("--track-qf", type=float, nargs="+", default=[1.0], help="one value, or one per state component")
+    ap.add_argument("--certify", action="store_true", help="also bracket the plans' true clearance (certify_batch)")
+    ap.add_argument("--certify-tol", type=float, default=1e-3)
     a = ap.parse_args(argv)
     for k in ("track_q", "track_r", "track_qf"):  # one value: a scalar for every component
         v = getattr(a, k)
@@ -113,6 +119,17 @@ def main(argv=None):
                             saturated_knots_quantiles={str(q): float(np.quantile(sat, q)) if n else None for q in qs},
                             verify_ok=int((flags == 0).sum()),
                             verify_ok_track_collides=int(((flags == 0) & ((tflags & hits) != 0)).sum()))
+    if a.certify:
+        from nlotrajectories_amd.certify import certify_batch
+
+        c = certify_batch(prob, X, obstacles=scene_obstacles(a.scene), tol=a.certify_tol)
+        cflags, ev = c["flags"].cpu().numpy()[solved], c["evals"].cpu().numpy()[solved]
+        hit = (cflags & (_abi.CERTIFY_COLLISION | _abi.CERTIFY_CONTAINS)) != 0
+        verdicts = lambda m: dict(clear=int((cflags[m] == 0).sum()), collision=int(hit[m].sum()),  # noqa: E731
+                                  undecided=int((~hit[m] & (cflags[m] != 0)).sum()))
+        out["certify"] = dict(tol=a.certify_tol, **verdicts(np.ones(n, bool)), verify_ok=verdicts(flags == 0),
+                              budget_share=float(((cflags & _abi.CERTIFY_BUDGET) != 0).mean()) if n else None,
+                              evals_mean=float(ev.mean()) if n else None, evals_max=int(ev.max()) if n else None)
     print(json.dumps(out))
 
 
