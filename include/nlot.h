@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 23
+#define NLOT_ABI_VERSION 24
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -226,12 +226,18 @@ NlotMlp* nlot_mlp_create(const NlotMlpDesc* desc);
  *                              do not fit in LDS: the waves of a block split a layer's units, the activations live in
  *                              LDS and the HxH weights stream from L2 in a fragment order made at creation.  Hidden
  *                              width 64, 128 or 256 with 1-4 HxH layers.  Opt-in like NLOT_MLP_ARITH_HDUAL_MFMA; refused
- *                              for ReLU nets and for nets without an HxH layer */
+ *                              for ReLU nets and for nets without an HxH layer
+ *   NLOT_MLP_ARITH_HDUAL_BF16  (ABI v24; smooth activations) the hyper-dual algorithm with every HxH product made from
+ *                              operands split into three bf16 parts, six v_mfma_f32_16x16x32_bf16 products per fp32
+ *                              product (fp32-equivalent, as NLOT_MLP_ARITH_SPLIT_BF16 for the ReLU nets); the split
+ *                              layers are resident in LDS.  Hidden width 128 with 1 HxH layer or 64 with 1-4; other
+ *                              smooth shapes take NLOT_MLP_ARITH_HDUAL_MFMA / _STREAM.  Opt-in; refused for ReLU nets */
 #define NLOT_MLP_ARITH_SPLIT_BF16 0
 #define NLOT_MLP_ARITH_F32 1
 #define NLOT_MLP_ARITH_SEQ 2
 #define NLOT_MLP_ARITH_HDUAL_MFMA 3
 #define NLOT_MLP_ARITH_HDUAL_STREAM 4
+#define NLOT_MLP_ARITH_HDUAL_BF16 5
 NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* desc, int32_t arith);
 void nlot_mlp_destroy(NlotMlp* mlp);
 

@@ -1,6 +1,6 @@
 // What the learned-SDF MLP kernel families share (internal): nlot_mlp_f32.hip, nlot_mlp_bf16.hip, nlot_mlp_stream.hip,
-// nlot_mlp_hdual.hip, nlot_mlp_hdual_stream.hip and nlot_mlp_ref.hip hold one family each behind the launcher declared
-// here; nlot_mlp.hip chooses among them.
+// nlot_mlp_hdual.hip, nlot_mlp_hdual_stream.hip, nlot_mlp_hdual_bf16.hip and nlot_mlp_ref.hip hold one family each
+// behind the launcher declared here; nlot_mlp.hip chooses among them.
 #pragma once
 #include "nlot_internal.h"
 
@@ -42,6 +42,16 @@ __device__ __forceinline__ float turns_fourier(float x) {
     float r = fmaf(j, -6.28318548202514648f, x);
     r = fmaf(j, 1.74845560e-7f, r);
     return r * 0.159154943091895336f;
+}
+
+// x = h + m + l in three bf16 parts (8 + 8 + 8 significant bits, exact up to 2^-24 relative): the operands of the
+// split-bf16 kernels (mlp_bf16, mlp_hdual_bf16)
+__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
+#pragma clang fp contract(off)  // x is the rounded fp32 input: never fuse its producer into the subtractions
+    h = (__bf16)x;
+    const float r = x - (float)h;  // exact
+    m = (__bf16)r;
+    l = (__bf16)(r - (float)m);    // exact difference
 }
 
 // row index (hidden unit) held by register r of a 32x32 accumulator on lane-half hl
@@ -173,9 +183,22 @@ inline const char* hdual_stream_refusal(int act, int H, int n_hidden) {
     return nullptr;
 }
 
+// NLOT_MLP_ARITH_HDUAL_BF16 keeps every HxH layer in LDS as three bf16 parts in fragment order (nlot_mlp_hdual_bf16.hip):
+// 96 KB hold one layer at H = 128 or four at H = 64
+__host__ __device__ constexpr int hdual_bf16_max_layers(int H) { return H == 128 ? 1 : H == 64 ? 4 : 0; }
+// null when mlp_hdual_bf16 serves the net, else why not (nlot_mlp_create_ex refuses with it before any device call)
+inline const char* hdual_bf16_refusal(int act, int H, int n_hidden) {
+    if (act == NLOT_ACT_RELU || n_hidden < 1 || n_hidden > hdual_bf16_max_layers(H))
+        return "NLOT_MLP_ARITH_HDUAL_BF16 serves smooth activations (tanh, sigmoid, leaky ReLU, sine) with hidden width "
+               "128 and 1 HxH layer or hidden width 64 and 1-4; other smooth shapes take NLOT_MLP_ARITH_HDUAL_MFMA or "
+               "NLOT_MLP_ARITH_HDUAL_STREAM, ReLU nets the reverse-sweep arithmetics";
+    return nullptr;
+}
+
 // One launcher per family, arguments as launch_mlp_strided's, which has checked w.n_hidden for the family: f32 takes
 // H <= 128 with 1 or 2 HxH layers, bf16 H = 128 with one HxH layer and w.Wp, hdual what hdual_refusal passes,
-// hdual_stream what hdual_stream_refusal passes and w.Wf, the others every width
+// hdual_stream what hdual_stream_refusal passes and w.Wf, hdual_bf16 what hdual_bf16_refusal passes and w.Wb, the others
+// every width
 int launch_mlp_f32(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                    const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_bf16(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
@@ -188,6 +211,8 @@ int launch_mlp_hdual(const MlpDev& w, const float* pts, int64_t n, const int* n_
                      const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_hdual_stream(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                             const float* lam, const MlpOut& out, bool full, hipStream_t stream);
+int launch_mlp_hdual_bf16(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
+                          const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_seq(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                    const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 

@@ -41,6 +41,8 @@ int launch_mlp_strided(const MlpDev& w, const float* pts, int64_t n, const int* 
         return launch_mlp_hdual(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
     if (w.arith == NLOT_MLP_ARITH_HDUAL_STREAM)  // every smooth net with HxH layers (nlot_mlp_create_ex checks)
         return launch_mlp_hdual_stream(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
+    if (w.arith == NLOT_MLP_ARITH_HDUAL_BF16)  // smooth nets whose split layers fit in LDS (nlot_mlp_create_ex checks)
+        return launch_mlp_hdual_bf16(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
     if (w.act != NLOT_ACT_RELU) {  // smooth activations: forward hyper-duals (the ReLU masks / reuse do not apply)
         if (w.n_hidden < 0 || w.n_hidden > kMaxStreamLayers) {
             set_error("MLP kernel: 0 to 4 hidden HxH layers are supported for smooth activations");
@@ -65,6 +67,26 @@ int launch_mlp_strided(const MlpDev& w, const float* pts, int64_t n, const int* 
 
 }  // namespace nlot
 
+// x = hi + mid + lo in three bf16 parts, round-to-nearest-even at each step (host, exact): the weight operands of the
+// split-bf16 kernels, as split3 makes the activations' on the device
+static void split3_host(float x, uint16_t (&part)[3]) {
+    auto bf16_rne = [](float v) -> uint16_t {
+        uint32_t u;
+        memcpy(&u, &v, 4);
+        return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+    };
+    auto bf16_f = [](uint16_t h) -> float {
+        const uint32_t u = (uint32_t)h << 16;
+        float f;
+        memcpy(&f, &u, 4);
+        return f;
+    };
+    part[0] = bf16_rne(x);
+    const float r = x - bf16_f(part[0]);
+    part[1] = bf16_rne(r);
+    part[2] = bf16_rne(r - bf16_f(part[1]));
+}
+
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
@@ -73,9 +95,9 @@ extern "C" NlotMlp* nlot_mlp_create(const NlotMlpDesc* d) { return nlot_mlp_crea
 extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
     using namespace nlot;
     if (arith != NLOT_MLP_ARITH_SPLIT_BF16 && arith != NLOT_MLP_ARITH_F32 && arith != NLOT_MLP_ARITH_SEQ &&
-        arith != NLOT_MLP_ARITH_HDUAL_MFMA && arith != NLOT_MLP_ARITH_HDUAL_STREAM) {
+        arith != NLOT_MLP_ARITH_HDUAL_MFMA && arith != NLOT_MLP_ARITH_HDUAL_STREAM && arith != NLOT_MLP_ARITH_HDUAL_BF16) {
         set_error("nlot_mlp_create_ex: arith must be NLOT_MLP_ARITH_SPLIT_BF16, NLOT_MLP_ARITH_F32, NLOT_MLP_ARITH_SEQ, "
-                  "NLOT_MLP_ARITH_HDUAL_MFMA or NLOT_MLP_ARITH_HDUAL_STREAM");
+                  "NLOT_MLP_ARITH_HDUAL_MFMA, NLOT_MLP_ARITH_HDUAL_STREAM or NLOT_MLP_ARITH_HDUAL_BF16");
         return nullptr;
     }
     if (arith == NLOT_MLP_ARITH_SEQ && d && d->act != NLOT_ACT_RELU) {
@@ -110,14 +132,22 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
             return nullptr;
         }
     }
+    if (arith == NLOT_MLP_ARITH_HDUAL_BF16) {
+        if (const char* why = hdual_bf16_refusal(d->act, d->hidden, d->n_hidden)) {
+            set_error(std::string("nlot_mlp_create_ex: ") + why);
+            return nullptr;
+        }
+    }
     const int H = d->hidden, L = d->n_hidden;
     const size_t nA = 2 * H, nb0 = H, nW = (size_t)L * H * H, nb = (size_t)L * H, nw = H;
     const bool split = arith == NLOT_MLP_ARITH_SPLIT_BF16;
     const size_t nWp = split ? (size_t)3 * H * H / 2 : 0;  // bf16 planes of layer 0, in float units
     const bool stream = arith == NLOT_MLP_ARITH_HDUAL_STREAM;
-    const size_t nWt = smooth && arith != NLOT_MLP_ARITH_HDUAL_MFMA && !stream ? nW : 0;  // transposed HxH layers (mlp_smooth)
+    const bool hbf16 = arith == NLOT_MLP_ARITH_HDUAL_BF16;
+    const size_t nWt = smooth && arith != NLOT_MLP_ARITH_HDUAL_MFMA && !stream && !hbf16 ? nW : 0;  // transposed HxH layers (mlp_smooth)
     const size_t nWf = stream ? nW : 0;  // HxH layers in fragment order (mlp_hdual_stream)
-    const size_t total = nA + nb0 + nW + nb + nw + nWp + nWt + nWf + 4;
+    const size_t nWb = hbf16 ? 3 * nW / 2 : 0;  // bf16 parts of the HxH layers in fragment order (mlp_hdual_bf16), in float units
+    const size_t total = nA + nb0 + nW + nb + nw + nWp + nWt + nWf + nWb + 4;
     float* blk = nullptr;
     if (hipMalloc(&blk, total * sizeof(float)) != hipSuccess) {
         set_error("nlot_mlp_create: hipMalloc failed");
@@ -149,26 +179,10 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
     m->dev.Wp = nullptr;
     if (L > 0 && split) {  // layer-0 weights split into three bf16 planes, round-to-nearest-even at each step (host, exact)
         std::vector<uint16_t> planes((size_t)3 * H * H);
-        auto bf16_rne = [](float x) -> uint16_t {
-            uint32_t u;
-            memcpy(&u, &x, 4);
-            return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-        };
-        auto bf16_f = [](uint16_t h) -> float {
-            const uint32_t u = (uint32_t)h << 16;
-            float f;
-            memcpy(&f, &u, 4);
-            return f;
-        };
         for (size_t i = 0; i < (size_t)H * H; ++i) {
-            const float x = d->W[i];
-            const uint16_t hi = bf16_rne(x);
-            const float r = x - bf16_f(hi);
-            const uint16_t mid = bf16_rne(r);
-            const uint16_t lo = bf16_rne(r - bf16_f(mid));
-            planes[i] = hi;
-            planes[(size_t)H * H + i] = mid;
-            planes[(size_t)2 * H * H + i] = lo;
+            uint16_t part[3];
+            split3_host(d->W[i], part);
+            for (int pl = 0; pl < 3; ++pl) planes[(size_t)pl * H * H + i] = part[pl];
         }
         m->dev.Wp = put(reinterpret_cast<const float*>(planes.data()), nWp);
     }
@@ -194,6 +208,23 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
                                 wf[q++] = d->W[(size_t)l * H * H + (size_t)(16 * (wave * NQ + t) + (lane & 15)) * H +
                                                16 * T + 4 * (lane >> 4) + j];
         m->dev.Wf = put(wf.data(), nWf);
+    }
+    m->dev.Wb = nullptr;
+    if (nWb) {  // [l][part][t][kb][lane][8]: the A operand a lane of mlp_hdual_bf16 loads for output tile t, k block kb
+        std::vector<uint16_t> wb(2 * nWb);
+        const int NT = H / 16, NKB = H / 32;
+        for (int l = 0; l < L; ++l)
+            for (int t = 0; t < NT; ++t)
+                for (int kb = 0; kb < NKB; ++kb)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int j = 0; j < 8; ++j) {
+                            uint16_t part[3];
+                            split3_host(d->W[(size_t)l * H * H + (size_t)(16 * t + (lane & 15)) * H + 32 * kb +
+                                             16 * (j >> 2) + 4 * (lane >> 4) + (j & 3)], part);
+                            for (int pl = 0; pl < 3; ++pl)
+                                wb[(((((size_t)l * 3 + pl) * NT + t) * NKB + kb) * 64 + lane) * 8 + j] = part[pl];
+                        }
+        m->dev.Wb = put(reinterpret_cast<const float*>(wb.data()), nWb);
     }
     if (hipDeviceSynchronize() != hipSuccess) {
         set_error("nlot_mlp_create: copy failed");

@@ -13,14 +13,6 @@
 
 namespace nlot {
 
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-#pragma clang fp contract(off)  // x is the rounded fp32 input: never fuse its producer into the subtractions
-    h = (__bf16)x;
-    const float r = x - (float)h;  // exact
-    m = (__bf16)r;
-    l = (__bf16)(r - (float)m);    // exact difference
-}
-
 // The five smaller split products of a k block into a running accumulator of their own; the hi x hi products go into
 // the main one and the two are added once per output tile by a VALU add (round to nearest).  One
 // v_mfma_f32_32x32x16_bf16 aligns its addends (the accumulator and its 16 products) to the largest of them and keeps

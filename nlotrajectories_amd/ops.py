@@ -20,9 +20,11 @@ class DeviceMlp:
     forward as hyper-duals through v_mfma_f32 products (mlp_hdual); opt-in, a smooth net with any other arith takes
     the scalar-FMA kernel mlp_smooth.  "hdual_stream" (smooth activations, hidden width 64, 128 or 256 with 1-4 HxH
     layers): the same arithmetic with the activations in LDS and the weights streamed from L2 (mlp_hdual_stream), for
-    the shapes "hdual_mfma" refuses; opt-in as well."""
+    the shapes "hdual_mfma" refuses; opt-in as well.  "hdual_bf16" (smooth activations, hidden width 128 with 1 HxH layer
+    or 64 with 1-4): the hyper-dual algorithm with every HxH product made from three-way split bf16 operands, six bf16
+    MFMA products per fp32 product (mlp_hdual_bf16); opt-in as well."""
 
-    ARITH = {"split_bf16": 0, "f32": 1, "seq": 2, "hdual_mfma": 3, "hdual_stream": 4}
+    ARITH = {"split_bf16": 0, "f32": 1, "seq": 2, "hdual_mfma": 3, "hdual_stream": 4, "hdual_bf16": 5}
 
     def __init__(self, weights: MlpWeights, arith: str = "split_bf16"):
         require_gpu()

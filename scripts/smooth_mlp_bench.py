@@ -13,7 +13,14 @@ L2) in the same mlp_smooth / kernel / mlp_smooth alternation on the shapes mlp_h
 stress shape) and a tanh net of H = 128 with 4 HxH layers, and on the artefact-shaped Fourier-tanh 2-128-128-1, where
 mlp_hdual is timed as a third contestant.  That mode writes profiles/smooth_mlp_stream_bench.json.
 
-    python scripts/smooth_mlp_bench.py [--arith hdual_mfma|hdual_stream] [--points 1000000] [--reps 20] [--warmup 3]
+--arith hdual_bf16 times mlp_hdual_bf16 (DeviceMlp(w, "hdual_bf16"): the split-bf16 MFMA products) against mlp_hdual
+in the order mlp_hdual / mlp_hdual_bf16 / mlp_hdual, so that the spread of the two mlp_hdual runs bounds the machine's
+share, with mlp_smooth's time as a third column, on the Fourier-tanh and SIREN 2-128-128-1 and a tanh 2-64x(4 HxH)-1.
+FLOP/s are fp32-equivalent (one split product counted as one), against the f32 MFMA peak and against the split-bf16
+roofline of 416.7 TFLOP/s (the bf16 MFMA peak over six).  That mode writes profiles/smooth_mlp_bf16_bench.json.
+
+    python scripts/smooth_mlp_bench.py [--arith hdual_mfma|hdual_stream|hdual_bf16] [--points 1000000] [--reps 20]
+                                       [--warmup 3]
 """
 import argparse
 import dataclasses
@@ -25,6 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 PEAK_TFLOPS = 157.3  # v_mfma_f32_16x16x4_f32: 256 FLOP / cycle / CU x 256 CUs x 2.4 GHz
+PEAK_SPLIT_TFLOPS = 416.7  # fp32-equivalent: the bf16 MFMA peak of 2500 TFLOP/s over six products per fp32 product
 
 
 def time_ms(mlp, pts, full, reps, warmup):
@@ -75,9 +83,39 @@ def stream_bench(a, pts):
     return out
 
 
+def bf16_bench(a, pts):
+    """The --arith hdual_bf16 mode: {net: {launch: times}}."""
+    import torch
+
+    from nlotrajectories_amd import _abi
+    from nlotrajectories_amd.nn import SIREN, MlpWeights, MultiLayerPerceptron
+    from nlotrajectories_amd.ops import DeviceMlp
+
+    torch.manual_seed(0)
+    nets = {"fourier_tanh_2-128-128-1": dataclasses.replace(MlpWeights.artefact(), act=_abi.ACT_TANH),
+            "siren_2-128-128-1": MlpWeights.from_module(SIREN(2, 128, 1, num_layers=3, omega_0=30)),
+            "mlp_tanh_2-64x5-1": MlpWeights.from_module(MultiLayerPerceptron(2, 64, 1, 5, "Tanh"))}
+    out = {}
+    for name, w in nets.items():
+        hdual, split, smooth = DeviceMlp(w, "hdual_mfma"), DeviceMlp(w, "hdual_bf16"), DeviceMlp(w, "f32")
+        res = {}
+        for launch, full in (("full", True), ("value", False)):
+            ha, sp, hb = (time_ms(m, pts, full, a.reps, a.warmup) for m in (hdual, split, hdual))
+            sm = time_ms(smooth, pts, full, a.reps, a.warmup)
+            flop = 2.0 * (6 if full else 1) * w.n_hidden * w.hidden ** 2 * a.points
+            res[launch] = dict(mlp_hdual_ms=[ha, hb], mlp_hdual_spread_ms=abs(ha - hb), mlp_hdual_bf16_ms=sp,
+                               mlp_smooth_ms=sm, speedup_over_hdual=min(ha, hb) / sp,
+                               gain_ms=min(ha, hb) - sp, flop_per_point=flop / a.points,
+                               mlp_hdual_bf16_tflops=flop / sp * 1e-9, mlp_hdual_tflops=flop / min(ha, hb) * 1e-9,
+                               mlp_hdual_bf16_share_of_f32_peak=flop / sp * 1e-9 / PEAK_TFLOPS,
+                               mlp_hdual_bf16_share_of_split_peak=flop / sp * 1e-9 / PEAK_SPLIT_TFLOPS)
+        out[name] = res
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arith", choices=["hdual_mfma", "hdual_stream"], default="hdual_mfma")
+    ap.add_argument("--arith", choices=["hdual_mfma", "hdual_stream", "hdual_bf16"], default="hdual_mfma")
     ap.add_argument("--points", type=int, default=1000000)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -98,6 +136,9 @@ def main():
     if a.arith == "hdual_stream":
         nets = {}
         out.update(arith=a.arith, nets=stream_bench(a, pts))
+    if a.arith == "hdual_bf16":
+        nets = {}
+        out.update(arith=a.arith, peak_split_tflops=PEAK_SPLIT_TFLOPS, nets=bf16_bench(a, pts))
     for name, w in nets.items():
         smooth, hdual = DeviceMlp(w, "f32"), DeviceMlp(w, "hdual_mfma")
         res = {}
@@ -111,7 +152,8 @@ def main():
         out["nets"][name] = res
     text = json.dumps(out)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    name = "smooth_mlp_stream_bench.json" if a.arith == "hdual_stream" else "smooth_mlp_bench.json"
+    name = {"hdual_stream": "smooth_mlp_stream_bench.json", "hdual_bf16": "smooth_mlp_bf16_bench.json"}.get(
+        a.arith, "smooth_mlp_bench.json")
     with open(os.path.join(ROOT, "profiles", name), "w") as f:
         f.write(text + "\n")
     print(text)
