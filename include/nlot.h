@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 24
+#define NLOT_ABI_VERSION 25
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -231,13 +231,20 @@ NlotMlp* nlot_mlp_create(const NlotMlpDesc* desc);
  *                              operands split into three bf16 parts, six v_mfma_f32_16x16x32_bf16 products per fp32
  *                              product (fp32-equivalent, as NLOT_MLP_ARITH_SPLIT_BF16 for the ReLU nets); the split
  *                              layers are resident in LDS.  Hidden width 128 with 1 HxH layer or 64 with 1-4; other
- *                              smooth shapes take NLOT_MLP_ARITH_HDUAL_MFMA / _STREAM.  Opt-in; refused for ReLU nets */
+ *                              smooth shapes take NLOT_MLP_ARITH_HDUAL_MFMA / _STREAM.  Opt-in; refused for ReLU nets
+ *   NLOT_MLP_ARITH_HDUAL_BF16_STREAM (ABI v25; smooth activations) the same split-bf16 hyper-dual products for the shapes
+ *                              whose split layers do not fit in LDS: the waves of a block split a layer's units, the
+ *                              activations live in LDS already split into their bf16 parts and the split HxH weights
+ *                              stream from L2 in a fragment order made at creation.  Hidden width 128 or 256 with 1-4
+ *                              HxH layers; width 64 takes NLOT_MLP_ARITH_HDUAL_BF16.  Opt-in; refused for ReLU nets and
+ *                              for nets without an HxH layer */
 #define NLOT_MLP_ARITH_SPLIT_BF16 0
 #define NLOT_MLP_ARITH_F32 1
 #define NLOT_MLP_ARITH_SEQ 2
 #define NLOT_MLP_ARITH_HDUAL_MFMA 3
 #define NLOT_MLP_ARITH_HDUAL_STREAM 4
 #define NLOT_MLP_ARITH_HDUAL_BF16 5
+#define NLOT_MLP_ARITH_HDUAL_BF16_STREAM 6
 NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* desc, int32_t arith);
 void nlot_mlp_destroy(NlotMlp* mlp);
 

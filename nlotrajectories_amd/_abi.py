@@ -23,6 +23,7 @@ ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_LEAKY_RELU, ACT_SINE = 0, 1, 2, 3, 4
 # nlot_mlp_create_ex's arithmetic (include/nlot.h NLOT_MLP_ARITH_*; ABI v21 adds the MFMA hyper-dual kernel)
 MLP_ARITH_SPLIT_BF16, MLP_ARITH_F32, MLP_ARITH_SEQ, MLP_ARITH_HDUAL_MFMA, MLP_ARITH_HDUAL_STREAM = 0, 1, 2, 3, 4
 MLP_ARITH_HDUAL_BF16 = 5
+MLP_ARITH_HDUAL_BF16_STREAM = 6
 MAX_OBS, MAX_VERTS, MAX_BODY, MAX_NU = 128, 512, 8, 4
 MAX_NX = 8
 

@@ -43,6 +43,8 @@ int launch_mlp_strided(const MlpDev& w, const float* pts, int64_t n, const int* 
         return launch_mlp_hdual_stream(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
     if (w.arith == NLOT_MLP_ARITH_HDUAL_BF16)  // smooth nets whose split layers fit in LDS (nlot_mlp_create_ex checks)
         return launch_mlp_hdual_bf16(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
+    if (w.arith == NLOT_MLP_ARITH_HDUAL_BF16_STREAM)  // smooth nets of H = 128 / 256 with HxH layers (nlot_mlp_create_ex checks)
+        return launch_mlp_hdual_bf16_stream(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
     if (w.act != NLOT_ACT_RELU) {  // smooth activations: forward hyper-duals (the ReLU masks / reuse do not apply)
         if (w.n_hidden < 0 || w.n_hidden > kMaxStreamLayers) {
             set_error("MLP kernel: 0 to 4 hidden HxH layers are supported for smooth activations");
@@ -95,9 +97,11 @@ extern "C" NlotMlp* nlot_mlp_create(const NlotMlpDesc* d) { return nlot_mlp_crea
 extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
     using namespace nlot;
     if (arith != NLOT_MLP_ARITH_SPLIT_BF16 && arith != NLOT_MLP_ARITH_F32 && arith != NLOT_MLP_ARITH_SEQ &&
-        arith != NLOT_MLP_ARITH_HDUAL_MFMA && arith != NLOT_MLP_ARITH_HDUAL_STREAM && arith != NLOT_MLP_ARITH_HDUAL_BF16) {
+        arith != NLOT_MLP_ARITH_HDUAL_MFMA && arith != NLOT_MLP_ARITH_HDUAL_STREAM && arith != NLOT_MLP_ARITH_HDUAL_BF16 &&
+        arith != NLOT_MLP_ARITH_HDUAL_BF16_STREAM) {
         set_error("nlot_mlp_create_ex: arith must be NLOT_MLP_ARITH_SPLIT_BF16, NLOT_MLP_ARITH_F32, NLOT_MLP_ARITH_SEQ, "
-                  "NLOT_MLP_ARITH_HDUAL_MFMA, NLOT_MLP_ARITH_HDUAL_STREAM or NLOT_MLP_ARITH_HDUAL_BF16");
+                  "NLOT_MLP_ARITH_HDUAL_MFMA, NLOT_MLP_ARITH_HDUAL_STREAM, NLOT_MLP_ARITH_HDUAL_BF16 or "
+                  "NLOT_MLP_ARITH_HDUAL_BF16_STREAM");
         return nullptr;
     }
     if (arith == NLOT_MLP_ARITH_SEQ && d && d->act != NLOT_ACT_RELU) {
@@ -138,16 +142,24 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
             return nullptr;
         }
     }
+    if (arith == NLOT_MLP_ARITH_HDUAL_BF16_STREAM) {
+        if (const char* why = hdual_bf16_stream_refusal(d->act, d->hidden, d->n_hidden)) {
+            set_error(std::string("nlot_mlp_create_ex: ") + why);
+            return nullptr;
+        }
+    }
     const int H = d->hidden, L = d->n_hidden;
     const size_t nA = 2 * H, nb0 = H, nW = (size_t)L * H * H, nb = (size_t)L * H, nw = H;
     const bool split = arith == NLOT_MLP_ARITH_SPLIT_BF16;
     const size_t nWp = split ? (size_t)3 * H * H / 2 : 0;  // bf16 planes of layer 0, in float units
     const bool stream = arith == NLOT_MLP_ARITH_HDUAL_STREAM;
     const bool hbf16 = arith == NLOT_MLP_ARITH_HDUAL_BF16;
-    const size_t nWt = smooth && arith != NLOT_MLP_ARITH_HDUAL_MFMA && !stream && !hbf16 ? nW : 0;  // transposed HxH layers (mlp_smooth)
+    const bool hbs = arith == NLOT_MLP_ARITH_HDUAL_BF16_STREAM;
+    const size_t nWt = smooth && arith != NLOT_MLP_ARITH_HDUAL_MFMA && !stream && !hbf16 && !hbs ? nW : 0;  // transposed HxH layers (mlp_smooth)
     const size_t nWf = stream ? nW : 0;  // HxH layers in fragment order (mlp_hdual_stream)
     const size_t nWb = hbf16 ? 3 * nW / 2 : 0;  // bf16 parts of the HxH layers in fragment order (mlp_hdual_bf16), in float units
-    const size_t total = nA + nb0 + nW + nb + nw + nWp + nWt + nWf + nWb + 4;
+    const size_t nWs = hbs ? 3 * nW / 2 : 0;  // the same parts in mlp_hdual_bf16_stream's per-wave fragment order, in float units
+    const size_t total = nA + nb0 + nW + nb + nw + nWp + nWt + nWf + nWb + nWs + 4;
     float* blk = nullptr;
     if (hipMalloc(&blk, total * sizeof(float)) != hipSuccess) {
         set_error("nlot_mlp_create: hipMalloc failed");
@@ -225,6 +237,24 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
                                 wb[(((((size_t)l * 3 + pl) * NT + t) * NKB + kb) * 64 + lane) * 8 + j] = part[pl];
                         }
         m->dev.Wb = put(reinterpret_cast<const float*>(wb.data()), nWb);
+    }
+    m->dev.Ws = nullptr;
+    if (nWs) {  // [l][wave][kb][t][part][lane][8]: the A operand a lane of mlp_hdual_bf16_stream loads for k block kb, its tile t
+        std::vector<uint16_t> ws(2 * nWs);
+        const int NKB = H / 32, NQ = H / 64;
+        for (int l = 0; l < L; ++l)
+            for (int wave = 0; wave < 4; ++wave)
+                for (int kb = 0; kb < NKB; ++kb)
+                    for (int t = 0; t < NQ; ++t)
+                        for (int lane = 0; lane < 64; ++lane)
+                            for (int j = 0; j < 8; ++j) {
+                                uint16_t part[3];
+                                split3_host(d->W[(size_t)l * H * H + (size_t)(16 * (wave * NQ + t) + (lane & 15)) * H +
+                                                 32 * kb + 8 * (lane >> 4) + j], part);
+                                for (int pl = 0; pl < 3; ++pl)
+                                    ws[((((((size_t)l * 4 + wave) * NKB + kb) * NQ + t) * 3 + pl) * 64 + lane) * 8 + j] = part[pl];
+                            }
+        m->dev.Ws = put(reinterpret_cast<const float*>(ws.data()), nWs);
     }
     if (hipDeviceSynchronize() != hipSuccess) {
         set_error("nlot_mlp_create: copy failed");

@@ -19,8 +19,13 @@ share, with mlp_smooth's time as a third column, on the Fourier-tanh and SIREN 2
 FLOP/s are fp32-equivalent (one split product counted as one), against the f32 MFMA peak and against the split-bf16
 roofline of 416.7 TFLOP/s (the bf16 MFMA peak over six).  That mode writes profiles/smooth_mlp_bf16_bench.json.
 
-    python scripts/smooth_mlp_bench.py [--arith hdual_mfma|hdual_stream|hdual_bf16] [--points 1000000] [--reps 20]
-                                       [--warmup 3]
+--arith hdual_bf16_stream times mlp_hdual_bf16_stream (DeviceMlp(w, "hdual_bf16_stream"): the split-bf16 products with
+the split activations in LDS and the split weights streamed) against mlp_hdual_stream in the order mlp_hdual_stream /
+mlp_hdual_bf16_stream / mlp_hdual_stream on the three nets of --arith hdual_stream, with the same fp32-equivalent
+FLOP/s and both peaks.  That mode writes profiles/smooth_mlp_bf16_stream_bench.json.
+
+    python scripts/smooth_mlp_bench.py [--arith hdual_mfma|hdual_stream|hdual_bf16|hdual_bf16_stream]
+                                       [--points 1000000] [--reps 20] [--warmup 3]
 """
 import argparse
 import dataclasses
@@ -113,9 +118,40 @@ def bf16_bench(a, pts):
     return out
 
 
+def bf16_stream_bench(a, pts):
+    """The --arith hdual_bf16_stream mode: {net: {launch: times}}."""
+    import torch
+
+    from nlotrajectories_amd import _abi
+    from nlotrajectories_amd.nn import MlpWeights, MultiLayerPerceptron
+    from nlotrajectories_amd.ops import DeviceMlp
+
+    torch.manual_seed(0)  # stream_bench's nets
+    nets = {"mlp_tanh_2-256x4-1": MlpWeights.from_module(MultiLayerPerceptron(2, 256, 1, 4, "Tanh")),
+            "mlp_tanh_2-128x5-1": MlpWeights.from_module(MultiLayerPerceptron(2, 128, 1, 5, "Tanh")),
+            "fourier_tanh_2-128-128-1": dataclasses.replace(MlpWeights.artefact(), act=_abi.ACT_TANH)}
+    out = {}
+    for name, w in nets.items():
+        stream, split = DeviceMlp(w, "hdual_stream"), DeviceMlp(w, "hdual_bf16_stream")
+        res = {}
+        for launch, full in (("full", True), ("value", False)):
+            sa, sp, sb = (time_ms(m, pts, full, a.reps, a.warmup) for m in (stream, split, stream))
+            flop = 2.0 * (6 if full else 1) * w.n_hidden * w.hidden ** 2 * a.points
+            res[launch] = dict(mlp_hdual_stream_ms=[sa, sb], mlp_hdual_stream_spread_ms=abs(sa - sb),
+                               mlp_hdual_bf16_stream_ms=sp, speedup_over_hdual_stream=min(sa, sb) / sp,
+                               gain_ms=min(sa, sb) - sp, flop_per_point=flop / a.points,
+                               mlp_hdual_bf16_stream_tflops=flop / sp * 1e-9,
+                               mlp_hdual_stream_tflops=flop / min(sa, sb) * 1e-9,
+                               mlp_hdual_bf16_stream_share_of_f32_peak=flop / sp * 1e-9 / PEAK_TFLOPS,
+                               mlp_hdual_bf16_stream_share_of_split_peak=flop / sp * 1e-9 / PEAK_SPLIT_TFLOPS)
+        out[name] = res
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arith", choices=["hdual_mfma", "hdual_stream", "hdual_bf16"], default="hdual_mfma")
+    ap.add_argument("--arith", choices=["hdual_mfma", "hdual_stream", "hdual_bf16", "hdual_bf16_stream"],
+                    default="hdual_mfma")
     ap.add_argument("--points", type=int, default=1000000)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -139,6 +175,9 @@ def main():
     if a.arith == "hdual_bf16":
         nets = {}
         out.update(arith=a.arith, peak_split_tflops=PEAK_SPLIT_TFLOPS, nets=bf16_bench(a, pts))
+    if a.arith == "hdual_bf16_stream":
+        nets = {}
+        out.update(arith=a.arith, peak_split_tflops=PEAK_SPLIT_TFLOPS, nets=bf16_stream_bench(a, pts))
     for name, w in nets.items():
         smooth, hdual = DeviceMlp(w, "f32"), DeviceMlp(w, "hdual_mfma")
         res = {}
@@ -152,8 +191,8 @@ def main():
         out["nets"][name] = res
     text = json.dumps(out)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    name = {"hdual_stream": "smooth_mlp_stream_bench.json", "hdual_bf16": "smooth_mlp_bf16_bench.json"}.get(
-        a.arith, "smooth_mlp_bench.json")
+    name = {"hdual_stream": "smooth_mlp_stream_bench.json", "hdual_bf16": "smooth_mlp_bf16_bench.json",
+            "hdual_bf16_stream": "smooth_mlp_bf16_stream_bench.json"}.get(a.arith, "smooth_mlp_bench.json")
     with open(os.path.join(ROOT, "profiles", name), "w") as f:
         f.write(text + "\n")
     print(text)
