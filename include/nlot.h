@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NLOT_ABI_VERSION 25
+#define NLOT_ABI_VERSION 26
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define NLOT_OK 0
@@ -237,7 +237,15 @@ NlotMlp* nlot_mlp_create(const NlotMlpDesc* desc);
  *                              activations live in LDS already split into their bf16 parts and the split HxH weights
  *                              stream from L2 in a fragment order made at creation.  Hidden width 128 or 256 with 1-4
  *                              HxH layers; width 64 takes NLOT_MLP_ARITH_HDUAL_BF16.  Opt-in; refused for ReLU nets and
- *                              for nets without an HxH layer */
+ *                              for nets without an HxH layer
+ *   NLOT_MLP_ARITH_SPLIT_BF16_STREAM (ABI v26; ReLU nets) the ReLU nets' forward pass and reverse sweep with every HxH
+ *                              product, W h and W^T e, made from operands split into three bf16 parts, for the shapes
+ *                              whose layers do not fit in LDS (which NLOT_MLP_ARITH_SPLIT_BF16 serves with v_mfma_f32
+ *                              products): the waves of a block split a layer's units, the activations and the reverse
+ *                              sweep's vector live in LDS already split, and the split HxH weights and their transposes
+ *                              stream from L2 in a fragment order made at creation.  Hidden width 128 or 256 with 1-4 HxH
+ *                              layers, Fourier or Linear+ReLU input layer.  Opt-in; refused for smooth activations and
+ *                              hidden width 64.  The solver's forward reuse does not apply */
 #define NLOT_MLP_ARITH_SPLIT_BF16 0
 #define NLOT_MLP_ARITH_F32 1
 #define NLOT_MLP_ARITH_SEQ 2
@@ -245,6 +253,7 @@ NlotMlp* nlot_mlp_create(const NlotMlpDesc* desc);
 #define NLOT_MLP_ARITH_HDUAL_STREAM 4
 #define NLOT_MLP_ARITH_HDUAL_BF16 5
 #define NLOT_MLP_ARITH_HDUAL_BF16_STREAM 6
+#define NLOT_MLP_ARITH_SPLIT_BF16_STREAM 7
 NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* desc, int32_t arith);
 void nlot_mlp_destroy(NlotMlp* mlp);
 

@@ -24,6 +24,7 @@ ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_LEAKY_RELU, ACT_SINE = 0, 1, 2, 3, 4
 MLP_ARITH_SPLIT_BF16, MLP_ARITH_F32, MLP_ARITH_SEQ, MLP_ARITH_HDUAL_MFMA, MLP_ARITH_HDUAL_STREAM = 0, 1, 2, 3, 4
 MLP_ARITH_HDUAL_BF16 = 5
 MLP_ARITH_HDUAL_BF16_STREAM = 6
+MLP_ARITH_SPLIT_BF16_STREAM = 7
 MAX_OBS, MAX_VERTS, MAX_BODY, MAX_NU = 128, 512, 8, 4
 MAX_NX = 8
 

@@ -124,7 +124,7 @@ def lib():
     L.nlot_certify_batch.restype = C.c_int32
     L.nlot_casadi_bind.argtypes = [vp]
     L.nlot_casadi_bind.restype = C.c_int32
-    if L.nlot_abi_version() != 25:
+    if L.nlot_abi_version() != 26:
         raise NlotError("libnlot.so ABI version mismatch")
     _lib = L
     return L

@@ -147,7 +147,8 @@ def run_benchmark(config_path, initializer="yaml", weights=None, results_dir="re
     bracket of the interpolated plan's clearance and its verdict.  mlp_arith: the learned SDF's
     arithmetic (DeviceMlp.ARITH; "hdual_mfma" puts a smooth-activation net on the MFMA hyper-dual kernel,
     "hdual_stream" on its streamed-weight variant, "hdual_bf16" on the split-bf16 hyper-dual kernel,
-    "hdual_bf16_stream" on that kernel's streamed-weight variant)."""
+    "hdual_bf16_stream" on that kernel's streamed-weight variant; "split_bf16_stream" puts a ReLU net of hidden width
+    128 or 256 on the streamed split-bf16 reverse-sweep kernel)."""
     config_path = Path(config_path)
     cfg = Config.load(config_path)
     if cfg.solver.type != "ipopt":
@@ -297,13 +298,15 @@ def _parser():
                     help="--weights train: the PyTorch loop, or the persistent HIP training kernel (the ReLU net "
                          "2-128-128-1 in batches of 256 only)")
     ap.add_argument("--mlp-arith", choices=["split_bf16", "f32", "seq", "hdual_mfma", "hdual_stream", "hdual_bf16",
-                                            "hdual_bf16_stream"],
+                                            "hdual_bf16_stream", "split_bf16_stream"],
                     default="split_bf16",
                     help="the learned SDF's kernel arithmetic (DeviceMlp); hdual_mfma: the MFMA hyper-dual kernel for "
                          "smooth activations (hidden width 128 with 1-2 HxH layers, 64 with 1-4); hdual_stream: its "
                          "streamed-weight variant (hidden width 64, 128 or 256 with 1-4 HxH layers); hdual_bf16: the "
                          "hyper-dual kernel on split-bf16 MFMA products (hidden width 128 with 1 HxH layer, 64 with 1-4); "
-                         "hdual_bf16_stream: its streamed-weight variant (hidden width 128 or 256 with 1-4 HxH layers)")
+                         "hdual_bf16_stream: its streamed-weight variant (hidden width 128 or 256 with 1-4 HxH layers); "
+                         "split_bf16_stream: the streamed split-bf16 kernel for ReLU nets (hidden width 128 or 256 with 1-4 "
+                         "HxH layers)")
     ap.add_argument("--train-sdf-device", choices=["host", "gpu"], default="host",
                     help="--weights train: where the training targets (the scene's exact SDF) are evaluated")
     return ap

@@ -90,7 +90,7 @@ struct MlpDev {
     int in_kind;     // NLOT_MLP_IN_*
     int H;           // hidden width
     int n_hidden;    // HxH layers
-    int act;         // NLOT_ACT_* (ReLU: the MFMA kernels; smooth activations: mlp_smooth, or mlp_hdual[_stream|_bf16|_bf16_stream] by arith)
+    int act;         // NLOT_ACT_* (ReLU: the MFMA kernels; smooth activations: mlp_smooth, or mlp_hdual[_stream|_bf16|_bf16_stream] by arith; ReLU: mlp_relu_bf16_stream by arith)
     float scale;     // fourier scale; omega_0 for NLOT_ACT_SINE
     float b_out;
     const float* A;     // [2][H]
@@ -106,10 +106,13 @@ struct MlpDev {
     // NLOT_MLP_ARITH_HDUAL_BF16 only: the HxH layers as three bf16 parts in MFMA fragment order [n_hidden][3 parts h, m, l]
     // [H/16 t][H/32 kb][64 lanes][8], lane (pn, lg) holding W[16 t + pn][32 kb + 16 (j >> 2) + 4 lg + (j & 3)] in slot j
     const void* Wb;
-    // NLOT_MLP_ARITH_HDUAL_BF16_STREAM only: the HxH layers as three bf16 parts in MFMA fragment order [n_hidden][4 waves]
+    // NLOT_MLP_ARITH_HDUAL_BF16_STREAM and NLOT_MLP_ARITH_SPLIT_BF16_STREAM only: the HxH layers as three bf16 parts in MFMA fragment order [n_hidden][4 waves]
     // [H/32 kb][H/64 t][3 parts h, m, l][64 lanes][8], lane (row, lg) holding W[16 (wave H/64 + t) + row][32 kb + 8 lg + j]
     // in slot j
     const void* Ws;
+    // NLOT_MLP_ARITH_SPLIT_BF16_STREAM only: the transposed HxH layers in Ws's order for the reverse sweep, the same lane
+    // holding W[32 kb + 8 lg + j][16 (wave H/64 + t) + row] in slot j
+    const void* Wr;
 };
 
 // Output addressing of the MLP kernel: element q of point i goes to ptr_q[i * stride_q].

@@ -1,6 +1,6 @@
 // What the learned-SDF MLP kernel families share (internal): nlot_mlp_f32.hip, nlot_mlp_bf16.hip, nlot_mlp_stream.hip,
-// nlot_mlp_hdual.hip, nlot_mlp_hdual_stream.hip, nlot_mlp_hdual_bf16.hip, nlot_mlp_hdual_bf16_stream.hip and
-// nlot_mlp_ref.hip hold one family each behind the launcher declared here; nlot_mlp.hip chooses among them.
+// nlot_mlp_hdual.hip, nlot_mlp_hdual_stream.hip, nlot_mlp_hdual_bf16.hip, nlot_mlp_hdual_bf16_stream.hip,
+// nlot_mlp_relu_bf16_stream.hip and nlot_mlp_ref.hip hold one family each behind the launcher declared here; nlot_mlp.hip chooses among them.
 #pragma once
 #include "nlot_internal.h"
 
@@ -45,7 +45,7 @@ __device__ __forceinline__ float turns_fourier(float x) {
 }
 
 // x = h + m + l in three bf16 parts (8 + 8 + 8 significant bits, exact up to 2^-24 relative): the operands of the
-// split-bf16 kernels (mlp_bf16, mlp_hdual_bf16, mlp_hdual_bf16_stream)
+// split-bf16 kernels (mlp_bf16, mlp_hdual_bf16, mlp_hdual_bf16_stream, mlp_relu_bf16_stream)
 __device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
 #pragma clang fp contract(off)  // x is the rounded fp32 input: never fuse its producer into the subtractions
     h = (__bf16)x;
@@ -206,10 +206,22 @@ inline const char* hdual_bf16_stream_refusal(int act, int H, int n_hidden) {
     return nullptr;
 }
 
+// NLOT_MLP_ARITH_SPLIT_BF16_STREAM keeps the split activations and the reverse sweep's e in LDS and streams the split
+// weights and their transposes (nlot_mlp_relu_bf16_stream.hip): null when mlp_relu_bf16_stream serves the net, else why
+// not (nlot_mlp_create_ex refuses with it before any device call)
+inline const char* relu_bf16_stream_refusal(int act, int H, int n_hidden) {
+    if (act != NLOT_ACT_RELU || (H != 128 && H != 256) || n_hidden < 1 || n_hidden > kMaxStreamLayers)
+        return "NLOT_MLP_ARITH_SPLIT_BF16_STREAM serves ReLU nets with hidden width 128 or 256 and 1-4 HxH layers; hidden "
+               "width 64 takes NLOT_MLP_ARITH_SPLIT_BF16 or NLOT_MLP_ARITH_F32 (the f32-MFMA kernels), smooth activations "
+               "NLOT_MLP_ARITH_HDUAL_BF16_STREAM, and a ReLU net needs an HxH layer in every arithmetic";
+    return nullptr;
+}
+
 // One launcher per family, arguments as launch_mlp_strided's, which has checked w.n_hidden for the family: f32 takes
 // H <= 128 with 1 or 2 HxH layers, bf16 H = 128 with one HxH layer and w.Wp, hdual what hdual_refusal passes,
 // hdual_stream what hdual_stream_refusal passes and w.Wf, hdual_bf16 what hdual_bf16_refusal passes and w.Wb,
-// hdual_bf16_stream what hdual_bf16_stream_refusal passes and w.Ws, the others every width
+// hdual_bf16_stream what hdual_bf16_stream_refusal passes and w.Ws, relu_bf16_stream what relu_bf16_stream_refusal
+// passes with w.Ws and w.Wr, the others every width
 int launch_mlp_f32(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                    const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_bf16(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
@@ -226,6 +238,8 @@ int launch_mlp_hdual_bf16(const MlpDev& w, const float* pts, int64_t n, const in
                           const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_hdual_bf16_stream(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                                  const float* lam, const MlpOut& out, bool full, hipStream_t stream);
+int launch_mlp_relu_bf16_stream(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
+                                const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 int launch_mlp_seq(const MlpDev& w, const float* pts, int64_t n, const int* n_dev, int P_per, int64_t ld,
                    const float* lam, const MlpOut& out, bool full, hipStream_t stream);
 

@@ -45,6 +45,8 @@ int launch_mlp_strided(const MlpDev& w, const float* pts, int64_t n, const int* 
         return launch_mlp_hdual_bf16(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
     if (w.arith == NLOT_MLP_ARITH_HDUAL_BF16_STREAM)  // smooth nets of H = 128 / 256 with HxH layers (nlot_mlp_create_ex checks)
         return launch_mlp_hdual_bf16_stream(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
+    if (w.arith == NLOT_MLP_ARITH_SPLIT_BF16_STREAM)  // ReLU nets of H = 128 / 256 (nlot_mlp_create_ex checks); no forward reuse
+        return launch_mlp_relu_bf16_stream(w, pts, n, n_dev, P_per, ld, lam, out, full, stream);
     if (w.act != NLOT_ACT_RELU) {  // smooth activations: forward hyper-duals (the ReLU masks / reuse do not apply)
         if (w.n_hidden < 0 || w.n_hidden > kMaxStreamLayers) {
             set_error("MLP kernel: 0 to 4 hidden HxH layers are supported for smooth activations");
@@ -89,6 +91,28 @@ static void split3_host(float x, uint16_t (&part)[3]) {
     part[2] = bf16_rne(r - bf16_f(part[1]));
 }
 
+// The HxH layers (transposed: their transposes) as three bf16 parts in the streamed split-bf16 kernels' fragment order
+// [l][wave][kb][t][part][lane][8]: the A operand a lane (row = lane & 15, lg = lane >> 4) of mlp_hdual_bf16_stream or
+// mlp_relu_bf16_stream loads for k block kb and its tile t, slot j holding M[16 (wave NQ + t) + row][32 kb + 8 lg + j] of
+// M = W_l or W_l^T
+static std::vector<uint16_t> stream_fragments(const float* W, int L, int H, bool transposed) {
+    std::vector<uint16_t> ws((size_t)3 * L * H * H);
+    const int NKB = H / 32, NQ = H / 64;
+    for (int l = 0; l < L; ++l)
+        for (int wave = 0; wave < 4; ++wave)
+            for (int kb = 0; kb < NKB; ++kb)
+                for (int t = 0; t < NQ; ++t)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int j = 0; j < 8; ++j) {
+                            const size_t r = 16 * (wave * NQ + t) + (lane & 15), k = 32 * kb + 8 * (lane >> 4) + j;
+                            uint16_t part[3];
+                            split3_host(W[(size_t)l * H * H + (transposed ? k * H + r : r * H + k)], part);
+                            for (int pl = 0; pl < 3; ++pl)
+                                ws[((((((size_t)l * 4 + wave) * NKB + kb) * NQ + t) * 3 + pl) * 64 + lane) * 8 + j] = part[pl];
+                        }
+    return ws;
+}
+
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
@@ -98,10 +122,10 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
     using namespace nlot;
     if (arith != NLOT_MLP_ARITH_SPLIT_BF16 && arith != NLOT_MLP_ARITH_F32 && arith != NLOT_MLP_ARITH_SEQ &&
         arith != NLOT_MLP_ARITH_HDUAL_MFMA && arith != NLOT_MLP_ARITH_HDUAL_STREAM && arith != NLOT_MLP_ARITH_HDUAL_BF16 &&
-        arith != NLOT_MLP_ARITH_HDUAL_BF16_STREAM) {
+        arith != NLOT_MLP_ARITH_HDUAL_BF16_STREAM && arith != NLOT_MLP_ARITH_SPLIT_BF16_STREAM) {
         set_error("nlot_mlp_create_ex: arith must be NLOT_MLP_ARITH_SPLIT_BF16, NLOT_MLP_ARITH_F32, NLOT_MLP_ARITH_SEQ, "
-                  "NLOT_MLP_ARITH_HDUAL_MFMA, NLOT_MLP_ARITH_HDUAL_STREAM, NLOT_MLP_ARITH_HDUAL_BF16 or "
-                  "NLOT_MLP_ARITH_HDUAL_BF16_STREAM");
+                  "NLOT_MLP_ARITH_HDUAL_MFMA, NLOT_MLP_ARITH_HDUAL_STREAM, NLOT_MLP_ARITH_HDUAL_BF16, "
+                  "NLOT_MLP_ARITH_HDUAL_BF16_STREAM or NLOT_MLP_ARITH_SPLIT_BF16_STREAM");
         return nullptr;
     }
     if (arith == NLOT_MLP_ARITH_SEQ && d && d->act != NLOT_ACT_RELU) {
@@ -116,6 +140,12 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
         (d->in_kind != NLOT_MLP_IN_FOURIER && d->in_kind != NLOT_MLP_IN_LINEAR_RELU)) {
         set_error("nlot_mlp_create: activation must be NLOT_ACT_* and the input layer Fourier or Linear+act");
         return nullptr;
+    }
+    if (arith == NLOT_MLP_ARITH_SPLIT_BF16_STREAM) {  // before the shape check: its refusals name the arithmetic
+        if (const char* why = relu_bf16_stream_refusal(d->act, d->hidden, d->n_hidden)) {
+            set_error(std::string("nlot_mlp_create_ex: ") + why);
+            return nullptr;
+        }
     }
     const bool smooth = d->act != NLOT_ACT_RELU;
     if ((d->hidden != 64 && d->hidden != 128 && d->hidden != 256) || d->n_hidden < (smooth ? 0 : 1) ||
@@ -155,11 +185,13 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
     const bool stream = arith == NLOT_MLP_ARITH_HDUAL_STREAM;
     const bool hbf16 = arith == NLOT_MLP_ARITH_HDUAL_BF16;
     const bool hbs = arith == NLOT_MLP_ARITH_HDUAL_BF16_STREAM;
+    const bool rbs = arith == NLOT_MLP_ARITH_SPLIT_BF16_STREAM;
     const size_t nWt = smooth && arith != NLOT_MLP_ARITH_HDUAL_MFMA && !stream && !hbf16 && !hbs ? nW : 0;  // transposed HxH layers (mlp_smooth)
     const size_t nWf = stream ? nW : 0;  // HxH layers in fragment order (mlp_hdual_stream)
     const size_t nWb = hbf16 ? 3 * nW / 2 : 0;  // bf16 parts of the HxH layers in fragment order (mlp_hdual_bf16), in float units
-    const size_t nWs = hbs ? 3 * nW / 2 : 0;  // the same parts in mlp_hdual_bf16_stream's per-wave fragment order, in float units
-    const size_t total = nA + nb0 + nW + nb + nw + nWp + nWt + nWf + nWb + nWs + 4;
+    const size_t nWs = hbs || rbs ? 3 * nW / 2 : 0;  // the same parts in the streamed kernels' per-wave fragment order, in float units
+    const size_t nWr = rbs ? 3 * nW / 2 : 0;  // and those of the transposed layers (mlp_relu_bf16_stream's reverse sweep)
+    const size_t total = nA + nb0 + nW + nb + nw + nWp + nWt + nWf + nWb + nWs + nWr + 4;
     float* blk = nullptr;
     if (hipMalloc(&blk, total * sizeof(float)) != hipSuccess) {
         set_error("nlot_mlp_create: hipMalloc failed");
@@ -239,23 +271,9 @@ extern "C" NlotMlp* nlot_mlp_create_ex(const NlotMlpDesc* d, int32_t arith) {
         m->dev.Wb = put(reinterpret_cast<const float*>(wb.data()), nWb);
     }
     m->dev.Ws = nullptr;
-    if (nWs) {  // [l][wave][kb][t][part][lane][8]: the A operand a lane of mlp_hdual_bf16_stream loads for k block kb, its tile t
-        std::vector<uint16_t> ws(2 * nWs);
-        const int NKB = H / 32, NQ = H / 64;
-        for (int l = 0; l < L; ++l)
-            for (int wave = 0; wave < 4; ++wave)
-                for (int kb = 0; kb < NKB; ++kb)
-                    for (int t = 0; t < NQ; ++t)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 8; ++j) {
-                                uint16_t part[3];
-                                split3_host(d->W[(size_t)l * H * H + (size_t)(16 * (wave * NQ + t) + (lane & 15)) * H +
-                                                 32 * kb + 8 * (lane >> 4) + j], part);
-                                for (int pl = 0; pl < 3; ++pl)
-                                    ws[((((((size_t)l * 4 + wave) * NKB + kb) * NQ + t) * 3 + pl) * 64 + lane) * 8 + j] = part[pl];
-                            }
-        m->dev.Ws = put(reinterpret_cast<const float*>(ws.data()), nWs);
-    }
+    if (nWs) m->dev.Ws = put(reinterpret_cast<const float*>(stream_fragments(d->W, L, H, false).data()), nWs);
+    m->dev.Wr = nullptr;
+    if (nWr) m->dev.Wr = put(reinterpret_cast<const float*>(stream_fragments(d->W, L, H, true).data()), nWr);
     if (hipDeviceSynchronize() != hipSuccess) {
         set_error("nlot_mlp_create: copy failed");
         hipFree(blk);

@@ -24,10 +24,13 @@ class DeviceMlp:
     or 64 with 1-4): the hyper-dual algorithm with every HxH product made from three-way split bf16 operands, six bf16
     MFMA products per fp32 product (mlp_hdual_bf16); opt-in as well.  "hdual_bf16_stream" (smooth activations, hidden
     width 128 or 256 with 1-4 HxH layers): the same split-bf16 products with the split activations in LDS and the split
-    weights streamed from L2 (mlp_hdual_bf16_stream), for the shapes "hdual_bf16" refuses; opt-in as well."""
+    weights streamed from L2 (mlp_hdual_bf16_stream), for the shapes "hdual_bf16" refuses; opt-in as well.  "split_bf16_stream" (ReLU nets,
+    hidden width 128 or 256 with 1-4 HxH layers): the forward pass and reverse sweep on split-bf16 products with the split
+    activations in LDS and the split weights and their transposes streamed from L2 (mlp_relu_bf16_stream), where
+    "split_bf16" runs v_mfma_f32 products (mlp_stream); opt-in as well."""
 
     ARITH = {"split_bf16": 0, "f32": 1, "seq": 2, "hdual_mfma": 3, "hdual_stream": 4, "hdual_bf16": 5,
-             "hdual_bf16_stream": 6}
+             "hdual_bf16_stream": 6, "split_bf16_stream": 7}
 
     def __init__(self, weights: MlpWeights, arith: str = "split_bf16"):
         require_gpu()
